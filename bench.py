@@ -8,7 +8,7 @@ bf16 autocast + CameraHead.forward (fp32) + pose decode — the north-star hot p
 Inputs are resident in HBM before the timed region.  Weights: the seeded synthetic
 rule (pretrained weights are not available offline).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 Multi-GPU: one process per GPU.  Launched by torch.distributed.run (WORLD_SIZE set) the
@@ -27,11 +27,19 @@ replicated camera head).  value = the scene's views / max-over-ranks time, scali
 group and the ranks_seen report without the model (gloo when no GPU is visible: the
 CPU test of the launcher).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with a
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: set up,
+--warmup steps, --steps timed steps (``ms_per_step`` = the timed region / --steps), the
+--dump-outputs files if asked for, the line; its ``roofline``, ``box_calibration`` and
+``cpu_baseline`` are null and ``extra_configs`` is empty.  --dump-outputs DIR writes what the
+last timed step returned (extrinsic, intrinsic, cam_tokens, rgbs of every query view) as
+DIR/<name>.npy; the inputs, the weights and the subsample draws are seeded, so the same
+arguments give the same arrays from run to run and from build to build.
+
+With --full the line also carries a
 ``roofline`` object for the dominant kernel class (live HIP-event timing inside
 the timed region) and a ``cpu_baseline`` object (the CPU oracle on a bounded
-sample, rank 0 at N=1 only).  A per-kernel-class breakdown goes to stderr.
-After the headline's timed region the same model also times the ``extra_configs`` (--extras):
+sample, rank 0 at N=1 only); a per-kernel-class breakdown goes to stderr; and
+after the headline's timed region the same model also times the ``extra_configs`` (--extras):
 N=64 @518 (the north star's 64-view scaling workload, sharded like the headline), on one GPU
 BASELINE C5 (N=128 @518 with fp8 global attention), and the headline workload at qk-norm gain 4
 (``g4``: trained-like q_norm / k_norm weights); they ride inside the one line and are never its
@@ -162,10 +170,19 @@ def algorithmic_tflop(n_views: int, img: int, C: int = 1024) -> float:
 
 def build_model(device, seed_rule=True):
     from sailrecon_amd.models.sail_recon import SailRecon
-    from sailrecon_amd.utils.synth_weights import synth_state_dict_like
+    from concurrent.futures import ThreadPoolExecutor
+
+    from sailrecon_amd.utils.synth_weights import synth_param
     torch.manual_seed(0)
     model = SailRecon(enable_point=False, enable_depth=False).eval()
-    sd = synth_state_dict_like(model) if seed_rule else None
+    sd = None
+    if seed_rule:
+        # synth_state_dict_like(model), key by key on a few threads: every key has its own seeded
+        # generator (the rule depends on the key's name and shape only), so the values are the same
+        # bits as the serial rule's, and the serial draws of 1.4 G values are most of a run's setup
+        shapes = [(k, tuple(v.shape)) for k, v in model.state_dict().items()]
+        with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
+            sd = dict(zip((k for k, _ in shapes), pool.map(lambda ks: synth_param(*ks), shapes)))
     if sd is not None:
         model.load_state_dict(sd)
     return model.to(device), sd
@@ -388,6 +405,31 @@ def ranks_report(device):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20   # all files of one --dump-outputs run together
+DUMP_SAMPLE_ELEMS = 1 << 20  # an output too large for its share is written as this many sampled elements
+
+
+def dump_outputs(out_dir: str, results, rank: int = 0, world: int = 1):
+    """Write what one step returned (SailRecon.forward: a list of per-view dicts) as
+    out_dir/<name>.npy, float32, each key stacked over the views (a rank of a multi-GPU run holds
+    its own query views and writes <name>.rank<r>.npy).  ``rgbs`` and ``images`` are the same
+    tensor (the query frames handed back), written once as ``rgbs``.  An array over its share of
+    DUMP_MAX_BYTES is written as DUMP_SAMPLE_ELEMS elements of the flattened array at fixed
+    seeded indices (sorted), so two builds sample the same positions."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    keys = [k for k in (results[0] if results else {}) if k != "images"]
+    share = DUMP_MAX_BYTES // max(1, len(keys))
+    for k in keys:
+        a = torch.stack([r[k] for r in results]).detach().float().cpu().contiguous()
+        if a.numel() * 4 > share:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, a.numel(), (min(DUMP_SAMPLE_ELEMS, share // 4),), generator=g).sort().values
+            a = a.view(-1)[idx]
+        name = k if world == 1 else f"{k}.rank{rank}"
+        np.save(os.path.join(out_dir, name + ".npy"), a.numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -421,7 +463,17 @@ def main():
                          "the kernels' behaviour under trained-weight statistics; reported in config")
     ap.add_argument("--launch-only", action="store_true",
                     help="launcher / process-group / ranks_seen check without the model (gloo if no GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure everything else the line can carry: the roofline (HIP "
+                         "events around the dominant class + --breakdown-steps instrumented steps), the "
+                         "extra_configs (--extras), the box calibration GEMM and the CPU baseline.  Without it "
+                         "a run sets up, warms up, times --steps steps and prints the line with those fields null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned (SailRecon.forward's "
+                         "per-view results, stacked over the views) as DIR/<name>.npy in float32")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_workers(args.gpus, sys.argv[1:]))
@@ -488,15 +540,22 @@ def main():
     # inside the timed region HIP events bracket the dominant class's launches only (DOMINANT_TAG,
     # the pair launch: 24 per step); events around every launch (~1,100 per step) cost the step host
     # and queue time, so the per-class breakdown comes from --breakdown-steps more steps after it
-    if not args.no_kernel_timing:
+    # (--full only: a plain run launches the steps untimed per kernel and reports roofline null)
+    if args.full and not args.no_kernel_timing:
         ops.TIMER = ops.KernelTimer(tags={DOMINANT_TAG})
     barrier()
+    last = None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    if args.steps > 0:
+        last = step()  # only the last step's results are kept (for --dump-outputs)
     barrier()
     dt = time.perf_counter() - t0
     timer_dom, ops.TIMER = ops.TIMER, None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, rank, world)
+    del last
     dt_t = torch.tensor([dt], device=device)
     if world > 1:
         dist.all_reduce(dt_t, op=dist.ReduceOp.MAX)
@@ -568,7 +627,7 @@ def main():
               file=sys.stderr)
 
     extras = []
-    if use_bf16 and not fp8:
+    if args.full and use_bf16 and not fp8:
         for name in [e for e in args.extras.split(",") if e and e != "none"]:
             if name in ("c5", "c5qk") and world > 1:
                 continue
@@ -578,10 +637,10 @@ def main():
                 continue  # the headline already runs at a scaled gain
             extras.append(extra_config(model, device, args, world, name))
 
-    calib = box_calibration(device) if use_bf16 else None
+    calib = box_calibration(device) if args.full and use_bf16 else None
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline({k: v for k, v in sd.items()}, args.img, n, args.cpu_views)
 
     if rank == 0:

@@ -1,6 +1,6 @@
 #!/usr/bin/env bash
 # final validation of a round (tools/final_job.sh A|B|C|D).  A = every GPU test but the multi-rank ones, B = the multi-rank tests +
-# smoke, C = default bench (cpu baseline, extras) + rocprofv3 kernel stats (1 and 3 steps: the
+# smoke, C = bench --full (cpu baseline, extras) + rocprofv3 kernel stats (1 and 3 steps: the
 # steady-state counts) + FETCH_SIZE / WRITE_SIZE PMC passes, D = training kernel stats + an unprofiled training step, E = the per-rank rehearsal (tools/rank_sim.py).
 set -u
 mkdir -p gpurun_out
@@ -20,7 +20,7 @@ case ${1:-} in
        --ignore tests/test_dist_gpu.py --ignore tests/test_train_step_gpu.py --ignore tests/test_c4_golden_gpu.py ;;
   B) run f_tests_b 1000 python -u -m pytest tests/test_dist_gpu.py tests/test_train_step_gpu.py tests/test_c4_golden_gpu.py -q -m gpu $T
      run f_smoke 200 python -c "import __graft_entry__ as g; g.smoke()" ;;
-  C) run f_bench 500 python bench.py
+  C) run f_bench 500 python bench.py --full
      run f_prof_s1 300 rocprofv3 --kernel-trace --stats -d gpurun_out/f_prof_s1 -o run --output-format csv -- python3 bench.py --steps 1 --warmup 1 $NB
      run f_prof_s3 300 rocprofv3 --kernel-trace --stats -d gpurun_out/f_prof_s3 -o run --output-format csv -- python3 bench.py --steps 3 --warmup 1 $NB
      run f_pmc_fetch 300 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/f_pmc_fetch -o run --output-format csv -- python3 bench.py --steps 1 --warmup 1 $NB

@@ -33,15 +33,15 @@ for step in "$@"; do
                   for c in 0 1 2; do run kattn_cfg${c}_$i 300 env SR_ATTN_CFG=$c SR_KB_STATIC=1 python tools/kbench.py attn || exit 1; done
                 done ;;
     smoke)   run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench)   run bench 600 python bench.py ;;
-    benchq)  run benchq 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline ;;
-    bench_c2) run bench_c2 400 python bench.py --views 8 --no-cpu-baseline ;;
-    bench64) run bench64 600 python bench.py --views 64 --steps 5 --warmup 2 --no-cpu-baseline ;;
+    bench)   run bench 600 python bench.py --full ;;
+    benchq)  run benchq 400 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline ;;
+    bench_c2) run bench_c2 400 python bench.py --full --views 8 --no-cpu-baseline ;;
+    bench64) run bench64 600 python bench.py --full --views 64 --steps 5 --warmup 2 --no-cpu-baseline ;;
     prof64)  run prof64 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof64 -o run --output-format csv -- \
                python3 bench.py --views 64 --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timing ;;
     bench_extra) run bench_extra 600 python bench.py --steps 4 --warmup 1 --no-cpu-baseline --extra-c5 qkv ;;
-    bench_c5) run bench_c5 600 python bench.py --views 128 --steps 2 --warmup 1 --no-cpu-baseline ;;
-    bench_c5q) run bench_c5q 600 python bench.py --views 128 --steps 2 --warmup 1 --no-cpu-baseline --fp8-global qkv ;;
+    bench_c5) run bench_c5 600 python bench.py --full --views 128 --steps 2 --warmup 1 --no-cpu-baseline ;;
+    bench_c5q) run bench_c5q 600 python bench.py --full --views 128 --steps 2 --warmup 1 --no-cpu-baseline --fp8-global qkv ;;
     kbench)  run kbench 300 python tools/kbench.py ;;
     kgemm)   run kgemm 300 python tools/kbench.py gemm ln ;;
     kgemm_128) for i in 1 2; do
