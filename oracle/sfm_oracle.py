@@ -341,7 +341,7 @@ def pose_encoding_to_extri_intri(enc: Tensor, hw: Tuple[int, int]) -> Tuple[Tens
     H, W = hw
     fy = (H / 2.0) / torch.tan(fov_h / 2.0)
     fx = (W / 2.0) / torch.tan(fov_w / 2.0)
-    intr = torch.zeros(enc.shape[:2] + (3, 3))
+    intr = torch.zeros(enc.shape[:2] + (3, 3), dtype=enc.dtype)
     intr[..., 0, 0] = fx
     intr[..., 1, 1] = fy
     intr[..., 0, 2] = W / 2
@@ -615,7 +615,8 @@ def reverse_transform_tensor(processed: Tensor, kp2k: Tensor, target: int, is_de
 # --------------------------------------------------------------------------
 # Self-supervised training loss: compute_loss (train/train_imc.py:141-246)
 # with CDFLossIndexPytorch (train/losses/cdf_loss.py:19-242) and the projective geometry of
-# train/utils/geometry.py:89-303.  Pinned by tests/golden/g8_loss.npz (reference modules).
+# train/utils/geometry.py:89-303.  Pinned by tests/golden/g8_loss.npz and g8b_loss_sweep.npz (reference
+# modules, fp32); follows the dtype of its inputs, so that in fp64 it checks the HIP kernel.
 # --------------------------------------------------------------------------
 
 def cdf_smooth_kernel(bin_width: float, gradient_smooth: float) -> Tensor:
@@ -638,18 +639,27 @@ def _reflect_conv(x: Tensor, taps: Tensor) -> Tensor:
     return sum(taps[k] * xp[:, k:k + x.shape[1]] for k in range(taps.numel()))
 
 
+def cdf_bins(res: Tensor, min_val: float, max_val: float, num_bins: int) -> Tuple[Tensor, Tensor]:
+    """(histogram bin, lookup bin) of each residual, unclamped (cdf_loss.py:136-139, 207-210):
+    truncation of (res - min) / bin_width, and of the same + 0.5."""
+    bw = (max_val - min_val) / num_bins
+    return ((res - min_val) / bw).long(), ((res - min_val) / bw + 0.5).long()
+
+
 def cdf_loss_values(res: Tensor, w: Tensor, node_src: Tensor, node_dst: Tensor, n_nodes: int,
                     min_val: float = 0.0, max_val: float = 15.0, num_bins: int = 250,
                     gradient_smooth: float = 0.05) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """CDFLossIndexPytorch.forward's values and gradients (cdf_loss.py:88-242):
-    (cdf_src, grad_src, cdf_dst, grad_dst), each [pairs, points]."""
+    (cdf_src, grad_src, cdf_dst, grad_dst), each [pairs, points].  Computes in res.dtype (the
+    Gaussian taps are the reference's fp32 values, cast up)."""
     P, K = res.shape
+    dt = res.dtype
     bw = (max_val - min_val) / num_bins
-    b = ((res - min_val) / bw).long()                                    # :136-139 histogram bin
-    ok = ((b >= 0) & (b < num_bins)).float()
+    b, bl = cdf_bins(res, min_val, max_val, num_bins)                     # :136-139 histogram bin
+    ok = ((b >= 0) & (b < num_bins)).to(dt)
     b = b.clamp(0, num_bins - 1)
-    hist = torch.zeros(n_nodes * num_bins)
-    tot = torch.zeros(n_nodes)
+    hist = torch.zeros(n_nodes * num_bins, dtype=dt)
+    tot = torch.zeros(n_nodes, dtype=dt)
     ns = node_src.long()[:, None].expand(P, K).reshape(-1)
     nd = node_dst.long()[:, None].expand(P, K).reshape(-1)
     hist.index_add_(0, ns * num_bins + b.reshape(-1), (w * ok).reshape(-1))
@@ -658,10 +668,9 @@ def cdf_loss_values(res: Tensor, w: Tensor, node_src: Tensor, node_dst: Tensor, 
     tot.index_add_(0, nd, w.reshape(-1))
     pmf = hist.view(n_nodes, num_bins) / (tot[:, None] + 1e-10)          # :177
     cdf = torch.cumsum(pmf, 1)
-    sobel = torch.tensor([-1.0, 0.0, 1.0]) / (2.0 * bw)                  # :59-60
-    pdf = _reflect_conv(_reflect_conv(cdf, sobel), cdf_smooth_kernel(bw, gradient_smooth))
-    bl = ((res - min_val) / bw + 0.5).long()                              # :207-210 lookup bin
-    valid = (bl >= 0) & (bl < num_bins) & (w > 0)
+    sobel = torch.tensor([-1.0, 0.0, 1.0], dtype=dt) / (2.0 * bw)        # :59-60
+    pdf = _reflect_conv(_reflect_conv(cdf, sobel), cdf_smooth_kernel(bw, gradient_smooth).to(dt))
+    valid = (bl >= 0) & (bl < num_bins) & (w > 0)                         # :207-210 lookup bin
     bl = bl.clamp(0, num_bins - 1)
     gs = node_src.long()[:, None] * num_bins + bl
     gd = node_dst.long()[:, None] * num_bins + bl
@@ -678,16 +687,19 @@ def _cdf_straight_through(res: Tensor, w: Tensor, *cdf_args) -> Tuple[Tensor, Te
     return cs + (res - res.detach()) * gs, cd + (res - res.detach()) * gd
 
 
-def imc_loss(enc: Tensor, hw: Tuple[int, int], kp2k: Tensor, shared_focal: bool, src_idx: Tensor, dst_idx: Tensor,
-             src_coords: Tensor, dst_coords: Tensor, src_depth: Tensor, dst_depth: Tensor, node_src: Tensor,
-             node_dst: Tensor, n_nodes: int, min_val: float = 0.0, max_val: float = 15.0, num_bins: int = 250,
-             gradient_smooth: float = 0.05) -> Tensor:
-    """compute_loss (train_imc.py:141-246) for pose encodings enc [N, 9] (differentiable)."""
+def imc_residuals(enc: Tensor, hw: Tuple[int, int], kp2k: Tensor, shared_focal: bool, src_idx: Tensor,
+                  dst_idx: Tensor, src_coords: Tensor, dst_coords: Tensor, src_depth: Tensor,
+                  dst_depth: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """The geometry of compute_loss (train_imc.py:141-238) in enc.dtype: log1p residuals of the
+    exact and the fixed-depth reprojection, each [pairs, points], and the projected depth p_z."""
+    dt = enc.dtype
+    kp2k, src_coords, dst_coords = kp2k.to(dt), src_coords.to(dt), dst_coords.to(dt)
+    src_depth, dst_depth = src_depth.to(dt), dst_depth.to(dt)
     ext, intr = pose_encoding_to_extri_intri(enc[None], hw)
     K = torch.bmm(kp2k, intr[0])                                           # :166 K' -> K
     if shared_focal:                                                      # :169-174
         K = K.mean(0, keepdim=True).repeat(K.shape[0], 1, 1)
-    pad = torch.tensor([0.0, 0.0, 0.0, 1.0])
+    pad = torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=dt)
 
     def pad44(e):                                                         # geometry.py pad_poses
         return torch.cat([e, pad.expand(e.shape[0], 1, 4)], 1)
@@ -700,11 +712,22 @@ def imc_loss(enc: Tensor, hw: Tuple[int, int], kp2k: Tensor, shared_focal: bool,
     p = torch.bmm(Kd, Y.transpose(1, 2)).transpose(1, 2)
     pred = p[..., :2] / (p[..., 2:] + 1e-6)                               # from_homogeneous
     pred2 = p[..., :2] / (dst_depth[..., None] + 1e-6)                    # approximation variant
-    w = torch.ones_like(src_depth)                                        # valid masks: all ones
+    res = [torch.log1p(torch.norm(pr - dst_coords, dim=-1)) for pr in (pred, pred2)]  # :212-238
+    return res[0], res[1], p[..., 2]
+
+
+def imc_loss(enc: Tensor, hw: Tuple[int, int], kp2k: Tensor, shared_focal: bool, src_idx: Tensor, dst_idx: Tensor,
+             src_coords: Tensor, dst_coords: Tensor, src_depth: Tensor, dst_depth: Tensor, node_src: Tensor,
+             node_dst: Tensor, n_nodes: int, min_val: float = 0.0, max_val: float = 15.0, num_bins: int = 250,
+             gradient_smooth: float = 0.05) -> Tensor:
+    """compute_loss (train_imc.py:141-246) for pose encodings enc [N, 9] (differentiable), computed
+    in enc.dtype throughout: fp32 restates the reference, fp64 is the HIP kernel's checker."""
+    r1, r2, _ = imc_residuals(enc, hw, kp2k, shared_focal, src_idx, dst_idx, src_coords, dst_coords, src_depth,
+                              dst_depth)
+    w = torch.ones_like(r1)                                               # valid masks: all ones
     args = (node_src, node_dst, n_nodes, min_val, max_val, num_bins, gradient_smooth)
     total = 0.0
-    for pr in (pred, pred2):
-        res = torch.log1p(torch.norm(pr - dst_coords, dim=-1))            # :212-238
+    for res in (r1, r2):
         a, b = _cdf_straight_through(res, w, *args)
         total = total + (a.mean() + b.mean()) / 2.0
     return total / 2.0

@@ -304,6 +304,29 @@ void check() {
   }
   expect("sr_imc_loss null", sr_imc_loss(nullptr, nullptr), false);
   std::printf("imc workspace floats: %lld\n", (long long)sr_imc_loss_workspace(4, 3, 1024, 1, 100));
+  {  // the sizes its fixed arrays hold (kr[64] / gKr[64], raw[1024], one reflection) are refused before any launch
+    sr_imc_loss_desc ld{};
+    ld.enc = fake<float>(0), ld.kp2k = fake<float>(1), ld.src_coords = fake<float>(2), ld.dst_coords = fake<float>(3);
+    ld.src_depth = fake<float>(4), ld.dst_depth = fake<float>(5), ld.smooth_w = fake<float>(6);
+    ld.src_idx = fake<int32_t>(7), ld.dst_idx = fake<int32_t>(8), ld.node_src = fake<int32_t>(9);
+    ld.node_dst = fake<int32_t>(10), ld.loss = fake<float>(11), ld.d_enc = fake<float>(12), ld.workspace = fake<float>(13);
+    ld.n_views = 64, ld.H = 392, ld.W = 518, ld.n_pairs = 70, ld.n_points = 130, ld.n_nodes = 64;
+    ld.min_val = 0.f, ld.max_val = 15.f, ld.num_bins = 1024, ld.smooth_radius = 13, ld.grad_scale = 1.f;
+    expect("sr_imc_loss 64 views 1024 bins", sr_imc_loss(nullptr, &ld), true);
+    sr_imc_loss_desc b = ld;
+    b.n_views = 65;
+    expect("sr_imc_loss 65 views", sr_imc_loss(nullptr, &b), false);
+    b = ld, b.num_bins = 1025;
+    expect("sr_imc_loss 1025 bins", sr_imc_loss(nullptr, &b), false);
+    b = ld, b.num_bins = 2, b.smooth_radius = 0;
+    expect("sr_imc_loss 2 bins", sr_imc_loss(nullptr, &b), false);
+    b = ld, b.num_bins = 3, b.smooth_radius = 2;
+    expect("sr_imc_loss 5 taps over 3 bins", sr_imc_loss(nullptr, &b), false);
+    b = ld, b.node_src = nullptr;
+    expect("sr_imc_loss null node_src", sr_imc_loss(nullptr, &b), false);
+    b = ld, b.max_val = 0.f;
+    expect("sr_imc_loss empty range", sr_imc_loss(nullptr, &b), false);
+  }
   expect("sr_pose_decode_f32 null", sr_pose_decode_f32(nullptr, nullptr, 9, 0, 518, 518, nullptr, nullptr), false);
   expect("sr_copy_rows_f32 null", sr_copy_rows_f32(nullptr, nullptr, 0, nullptr, 0, nullptr, 0, 0), false);
   expect("sr_conv3x3_f32 null", sr_conv3x3_f32(nullptr, nullptr, 1, 8, 8, 32, 1, 0, nullptr, 32, SR_EPI_BIAS, &ep, nullptr, 32, nullptr), false);

@@ -66,11 +66,10 @@ def imc_loss(pose_enc: Tensor, hw: Tuple[int, int], K_prime_to_K: Tensor, shared
     f = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
     i = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()  # noqa: E731
     tabs = cdf.device_tables(dev)
-    if tabs["src"].numel() == 1 and P > 1:
-        raise IndexError("CDFLossIndexPytorch built on single-entry indices cannot index more than one pair "
-                         "(cdf_loss.py:147-148)")
-    node_src = tabs["src"] if tabs["src"].numel() >= P else None
-    node_dst = tabs["dst"] if tabs["dst"].numel() >= P else None
+    if tabs["src"].numel() < P or tabs["dst"].numel() < P:
+        raise IndexError(f"CDFLossIndexPytorch built on {tabs['src'].numel()} / {tabs['dst'].numel()} src / dst "
+                         f"indices cannot index {P} pairs (cdf_loss.py:147-148)")
+    node_src, node_dst = tabs["src"], tabs["dst"]
     loss = loss_out if loss_out is not None else torch.empty(1, device=dev, dtype=torch.float32)
     d_enc = d_enc_out if d_enc_out is not None else torch.empty(n, 9, device=dev, dtype=torch.float32)
     L = _lib.load()

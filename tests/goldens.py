@@ -157,3 +157,63 @@ def parity_tol(key: str, mode: str) -> float:
     class, feature maps and camera tokens the "feat" class."""
     cls = "pose" if any(t in key for t in ("pose", "extrinsic", "intrinsic")) else "feat"
     return PARITY_TOL[mode][cls]
+
+
+# ---------------------------------------------------------------- IMC loss goldens (§8(f) rank 4)
+LOSS_G8 = ("dummy", "shared", "multi")
+LOSS_G8B = ("nonsquare", "window", "nosmooth", "bins1024", "v64", "sparse_nodes", "one_point")
+LOSS_GROUPS = {"T": slice(0, 3), "quat": slice(3, 7), "fov_h": slice(7, 8), "fov_w": slice(8, 9)}
+_LOSS_FILES = {}
+_LOSS_ORACLE = {}
+
+
+def loss_case(name):
+    """One case of g8_loss.npz / g8b_loss_sweep.npz (tests/golden/make_golden_loss.py) as tensors
+    plus settings; g8's cases carry the one setting that file was made with."""
+    fname = "g8_loss.npz" if name in LOSS_G8 else "g8b_loss_sweep.npz"
+    if fname not in _LOSS_FILES:
+        _LOSS_FILES[fname] = load_npz(fname)
+    z = _LOSS_FILES[fname]
+    c = {k: torch.from_numpy(z[f"{name}/{k}"]) for k in
+         ("enc", "kp2k", "src_idx", "dst_idx", "src_coords", "dst_coords", "src_depth", "dst_depth", "nodes_src",
+          "nodes_dst", "out_loss", "out_grad")}
+    c["shared"] = bool(z[f"{name}/shared"])
+    if name in LOSS_G8:
+        c.update(H=518, W=518, min_val=0.0, max_val=15.0, num_bins=250, gradient_smooth=0.05,
+                 num_nodes=int(max(c["nodes_src"].max(), c["nodes_dst"].max())) + 1)
+    else:
+        for k, t in (("H", int), ("W", int), ("min_val", float), ("max_val", float), ("num_bins", int),
+                     ("gradient_smooth", float), ("num_nodes", int)):
+            c[k] = t(z[f"{name}/{k}"])
+    return c
+
+
+def loss_geometry_args(c, dtype):
+    return (c["enc"].to(dtype), (c["H"], c["W"]), c["kp2k"], c["shared"], c["src_idx"], c["dst_idx"],
+            c["src_coords"], c["dst_coords"], c["src_depth"], c["dst_depth"])
+
+
+def loss_oracle(name, dtype=torch.float64):
+    """(loss, d loss / d enc) of oracle.sfm_oracle.imc_loss in ``dtype``; computed once per case
+    and shared (callers do not modify the result)."""
+    key = (name, dtype)
+    if key not in _LOSS_ORACLE:
+        from oracle import sfm_oracle as O
+        c = loss_case(name)
+        args = loss_geometry_args(c, dtype)
+        enc = args[0].clone().requires_grad_(True)
+        loss = O.imc_loss(enc, *args[1:], c["nodes_src"], c["nodes_dst"], c["num_nodes"], c["min_val"],
+                          c["max_val"], c["num_bins"], c["gradient_smooth"])
+        loss.backward()
+        _LOSS_ORACLE[key] = (loss.detach(), enc.grad)
+    return _LOSS_ORACLE[key]
+
+
+def loss_errors(loss, grad, name):
+    """Errors of one (loss, [N, 9] gradient) against the fp64 oracle of case ``name``: relative
+    loss error and rel-L2 over the views per column group of LOSS_GROUPS."""
+    ol, og = loss_oracle(name)
+    out = {"loss": abs(float(loss) - float(ol)) / abs(float(ol))}
+    for k, s in LOSS_GROUPS.items():
+        out[k] = rel_l2(grad.double()[:, s], og[:, s])
+    return out

@@ -303,3 +303,53 @@ def test_oracle_imc_loss_matches_reference(golden_dir, case):
     assert abs(float(loss) - float(z[f"{case}/out_loss"])) <= 1e-6 * abs(float(z[f"{case}/out_loss"]))
     ref = g("out_grad")
     assert float((enc.grad - ref).norm() / ref.norm()) < 1e-5
+
+
+# ---------------------------------------------------------------- g8b: the loss sweep
+from goldens import LOSS_G8, LOSS_G8B, loss_case, loss_geometry_args, loss_oracle  # noqa: E402
+
+
+@pytest.mark.parametrize("case", LOSS_G8B)
+def test_oracle_imc_loss_matches_reference_sweep(case):
+    """fp32 oracle vs the reference modules on g8b_loss_sweep.npz (non-square images, CDF window,
+    no smoothing, 1024 bins, 64 views, sparse nodes, one point), at the bounds of the g8 test."""
+    c = loss_case(case)
+    loss, grad = loss_oracle(case, torch.float32)
+    ref_l = float(c["out_loss"])
+    assert abs(float(loss) - ref_l) <= 1e-6 * abs(ref_l)
+    assert rel_l2(grad, c["out_grad"]) < 1e-5
+
+
+def _fp64_residuals(case):
+    c = loss_case(case)
+    r1, r2, _ = O.imc_residuals(*loss_geometry_args(c, torch.float64))
+    return c, torch.stack([r1, r2])
+
+
+@pytest.mark.parametrize("case", LOSS_G8B)
+def test_loss_sweep_inputs_clear_of_bin_edges(case):
+    """The generator's redraw loop left no stored point within delta = min(1e-3, bin_width / 20) of
+    a histogram edge or a +0.5 lookup edge (multiples of bin_width / 2 from min_val) under the
+    fp64 oracle, so the GPU parity test compares every point; the window case keeps 10-60 % of
+    its residuals outside [min, max), some on each side."""
+    c, res = _fp64_residuals(case)
+    half = (c["max_val"] - c["min_val"]) / c["num_bins"] / 2
+    delta = min(1e-3, half / 10)
+    x = (res - c["min_val"]) / half
+    dist = (x - torch.round(x)).abs() * half
+    assert int((dist < delta).sum()) == 0, f"{int((dist < delta).sum())} points within {delta} of an edge"
+    if case == "window":
+        above, below = float((res >= c["max_val"]).double().mean()), float((res < c["min_val"]).double().mean())
+        print(f"window: above {above:.3f} below {below:.3f}")
+        assert above > 0 and below > 0 and 0.10 <= above + below <= 0.60
+
+
+@pytest.mark.parametrize("case", LOSS_G8B)
+def test_loss_sweep_bins_agree_fp32_fp64(case):
+    """Histogram bin and lookup bin of every point: fp64 oracle == fp32 oracle."""
+    c, res64 = _fp64_residuals(case)
+    r1, r2, _ = O.imc_residuals(*loss_geometry_args(c, torch.float32))
+    cdf = (c["min_val"], c["max_val"], c["num_bins"])
+    h64, l64 = O.cdf_bins(res64, *cdf)
+    h32, l32 = O.cdf_bins(torch.stack([r1, r2]), *cdf)
+    assert torch.equal(h64, h32) and torch.equal(l64, l32)
