@@ -814,6 +814,69 @@ int sr_pil_resample_v_f32(sr_stream_t stream, int mode, const void* tmp, int n, 
 int sr_resize_crop_chw_f32(sr_stream_t stream, const float* x, int c, int h, int w, int hs, int ws, int y0, int x0,
                            int ho, int wo, int mode, float* out);
 
+/* ------------------------------------------------------------------------------------------
+ * Training correspondences and depths (ABI 1.6): sample_correspondence_and_depth
+ * (train/utils/io.py:280-360), called once per ordered pair by IMC2021._create_downsampled_arrays
+ * (train/datasets/imc2021.py:317-390); here every pair of a scene in one launch sequence.
+ * Per pair p and sample k < n_points, with u = uniforms[p][k] in [0, 1):
+ *   w_i  = certainty_i > min_conf ? certainty_i : 0            (strict, fp32)
+ *   cdf  = inclusive prefix sum of w in fp64 (fixed partition and order: bit-stable), T = cdf[m-1]
+ *   idx  = first i with cdf[i] > u * T  (the last positive-weight index if rounding puts u * T >= T)
+ *   src_coords / dst_coords[p][k] = ((c_x + 1) * (W - 1) / 2, (c_y + 1) * (H - 1) / 2) of coords[idx],
+ *          fp32 and bit-equal to numpy, (H, W) the pair's own source / destination depth map size
+ *   src_depth / dst_depth[p][k] = F.grid_sample(depth, coords[idx], bilinear, zeros,
+ *          align_corners=False); tap indices are clamped before any load
+ *   total[p] = T, n_valid[p] = #{certainty_i > min_conf}; a pair with T == 0 gets zeros in every
+ *          output (the caller reports it); n_valid[p] = -1 marks a record the launch cannot hold
+ *          (m <= 0 or m > max_m, a non-positive size, a null pointer, an unknown format)
+ * numpy's np.random.choice(p = certainty / sum) returns the same idx for every u at least 2^-22
+ * (CDF units) from every edge of its CDF (csrc/sr_corres.hip).
+ * ------------------------------------------------------------------------------------------ */
+enum sr_corres_format {
+  SR_CORRES_F32 = 0,   /* src / dst: coords [m][2] fp32 in [-1, 1]; conf: certainty [m] fp32 */
+  SR_CORRES_PNG16 = 1  /* the matcher's stored maps, uint16 [hs][ws] each: dst = x, dst_y = y (decoded
+                          v / 65535 * 2 - 1, IMC2021._png2coords), conf = confidence (v / 1000,
+                          _png2certainty); coords_src is the implicit np.linspace(-1 + 1/ws, 1 - 1/ws, ws)
+                          x linspace(..hs..) grid of imc2021.py:126-131 rounded to fp32; m = hs * ws */
+};
+
+/* One pair's record; the table lives in DEVICE memory (one upload per call). */
+typedef struct sr_corres_pair {
+  const void* src;          /* F32: coords_src; PNG16: unused */
+  const void* dst;          /* F32: coords_dst; PNG16: x map */
+  const void* dst_y;        /* PNG16: y map; F32: unused */
+  const void* conf;
+  const float* depth_src;   /* [h1][w1] fp32 */
+  const float* depth_dst;   /* [h2][w2] fp32 */
+  int32_t format;           /* sr_corres_format */
+  int32_t m;                /* F32: correspondences (PNG16: hs * ws is used) */
+  int32_t hs, ws;           /* PNG16 */
+  int32_t h1, w1, h2, w2;
+} sr_corres_pair;
+
+typedef struct sr_corres_desc {
+  int n_pairs, n_points;
+  const sr_corres_pair* pairs;  /* [n_pairs], device */
+  int max_m;                    /* >= every pair's m: sizes the launch and the workspace */
+  const double* uniforms;       /* [n_pairs][n_points] in [0, 1) */
+  float min_conf;
+  float* src_coords;            /* [n_pairs][n_points][2] */
+  float* dst_coords;
+  float* src_depth;             /* [n_pairs][n_points] */
+  float* dst_depth;
+  int32_t* index;               /* [n_pairs][n_points] or NULL */
+  double* total;                /* [n_pairs] */
+  int32_t* n_valid;             /* [n_pairs] */
+  double* workspace;            /* the chunk-local fp64 CDFs and the chunk totals */
+  int64_t workspace_doubles;    /* >= sr_corres_sample_workspace(n_pairs, max_m), checked */
+} sr_corres_desc;
+
+/* doubles of workspace (8-B aligned, stream-ordered reuse) for n_pairs pairs of at most max_m entries */
+int64_t sr_corres_sample_workspace(int n_pairs, int max_m);
+/* Three launches (chunk scans, chunk prefixes, samples), asynchronous and allocation-free.  SR_EINVAL
+ * for a null pointer, n_points <= 0, n_pairs <= 0, max_m <= 0 or an undersized workspace. */
+int sr_corres_sample(sr_stream_t stream, const sr_corres_desc* desc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,8 @@
 //
 //   abi_host_check layout   JSON: size and field offsets of every ABI struct (tests/test_abi.py
 //                           compares them with the ctypes mirror in sailrecon_amd/_lib.py)
+//   abi_host_check layout corres   the same for the structs of sr_corres_sample (ABI 1.6), apart:
+//                           tests/test_debug_build.py pins the set the plain mode prints
 //   abi_host_check check    the validation sweep; exit 0 iff every call returned what it should
 #include <cstddef>
 #include <cstdio>
@@ -102,6 +104,23 @@ void layout() {
          (FIELD(sr_weight_item, src), FIELD(sr_weight_item, lds), FIELD(sr_weight_item, rows),
           FIELD(sr_weight_item, cols), FIELD(sr_weight_item, rowscale), FIELD(sr_weight_item, cast),
           FIELD(sr_weight_item, ldc), FIELD(sr_weight_item, trans), FIELD(sr_weight_item, ldt)));
+  std::printf("}\n");
+}
+
+void layout_corres() {
+  const char* sep = "";
+  std::printf("{");
+  STRUCT(sr_corres_pair,
+         (FIELD(sr_corres_pair, src), FIELD(sr_corres_pair, dst), FIELD(sr_corres_pair, dst_y),
+          FIELD(sr_corres_pair, conf), FIELD(sr_corres_pair, depth_src), FIELD(sr_corres_pair, depth_dst),
+          FIELD(sr_corres_pair, format), FIELD(sr_corres_pair, m), FIELD(sr_corres_pair, hs), FIELD(sr_corres_pair, ws),
+          FIELD(sr_corres_pair, h1), FIELD(sr_corres_pair, w1), FIELD(sr_corres_pair, h2), FIELD(sr_corres_pair, w2)));
+  STRUCT(sr_corres_desc,
+         (FIELD(sr_corres_desc, n_pairs), FIELD(sr_corres_desc, n_points), FIELD(sr_corres_desc, pairs),
+          FIELD(sr_corres_desc, max_m), FIELD(sr_corres_desc, uniforms), FIELD(sr_corres_desc, min_conf),
+          FIELD(sr_corres_desc, src_coords), FIELD(sr_corres_desc, dst_coords), FIELD(sr_corres_desc, src_depth),
+          FIELD(sr_corres_desc, dst_depth), FIELD(sr_corres_desc, index), FIELD(sr_corres_desc, total),
+          FIELD(sr_corres_desc, n_valid), FIELD(sr_corres_desc, workspace), FIELD(sr_corres_desc, workspace_doubles)));
   std::printf("}\n");
 }
 
@@ -327,6 +346,39 @@ void check() {
     b = ld, b.max_val = 0.f;
     expect("sr_imc_loss empty range", sr_imc_loss(nullptr, &b), false);
   }
+  expect("sr_corres_sample null", sr_corres_sample(nullptr, nullptr), false);
+  {  // ABI 1.6: null pointers, empty sizes and an undersized workspace are refused before any launch
+    const int64_t need = sr_corres_sample_workspace(240, 313600);
+    if (need < 240LL * 313600 || sr_corres_sample_workspace(0, 100) != 0 || sr_corres_sample_workspace(3, 0) != 0) ++g_fail;
+    std::printf("corres workspace doubles: %lld\n", (long long)need);
+    sr_corres_desc cd{};
+    cd.n_pairs = 240, cd.n_points = 10000, cd.max_m = 313600, cd.min_conf = 0.1f;
+    cd.pairs = fake<sr_corres_pair>(0), cd.uniforms = fake<double>(1);
+    cd.src_coords = fake<float>(2), cd.dst_coords = fake<float>(3), cd.src_depth = fake<float>(4), cd.dst_depth = fake<float>(5);
+    cd.total = fake<double>(6), cd.n_valid = fake<int32_t>(7), cd.workspace = fake<double>(8), cd.workspace_doubles = need;
+    expect("sr_corres_sample 240 pairs, no index", sr_corres_sample(nullptr, &cd), true);
+    sr_corres_desc b = cd;
+    b.workspace_doubles = need - 1;
+    expect("sr_corres_sample workspace one double short", sr_corres_sample(nullptr, &b), false);
+    b = cd, b.n_points = 0;
+    expect("sr_corres_sample 0 points", sr_corres_sample(nullptr, &b), false);
+    b = cd, b.n_pairs = 0;
+    expect("sr_corres_sample 0 pairs", sr_corres_sample(nullptr, &b), false);
+    b = cd, b.max_m = 0;
+    expect("sr_corres_sample max_m 0", sr_corres_sample(nullptr, &b), false);
+    b = cd, b.pairs = nullptr;
+    expect("sr_corres_sample null table", sr_corres_sample(nullptr, &b), false);
+    b = cd, b.uniforms = nullptr;
+    expect("sr_corres_sample null uniforms", sr_corres_sample(nullptr, &b), false);
+    b = cd, b.total = nullptr;
+    expect("sr_corres_sample null total", sr_corres_sample(nullptr, &b), false);
+    b = cd, b.dst_depth = nullptr;
+    expect("sr_corres_sample null output", sr_corres_sample(nullptr, &b), false);
+    b = cd, b.workspace = nullptr;
+    expect("sr_corres_sample null workspace", sr_corres_sample(nullptr, &b), false);
+    b = cd, b.n_pairs = 70000, b.workspace_doubles = sr_corres_sample_workspace(70000, 313600);
+    expect("sr_corres_sample 70000 pairs", sr_corres_sample(nullptr, &b), false);
+  }
   expect("sr_pose_decode_f32 null", sr_pose_decode_f32(nullptr, nullptr, 9, 0, 518, 518, nullptr, nullptr), false);
   expect("sr_copy_rows_f32 null", sr_copy_rows_f32(nullptr, nullptr, 0, nullptr, 0, nullptr, 0, 0), false);
   expect("sr_conv3x3_f32 null", sr_conv3x3_f32(nullptr, nullptr, 1, 8, 8, 32, 1, 0, nullptr, 32, SR_EPI_BIAS, &ep, nullptr, 32, nullptr), false);
@@ -363,7 +415,10 @@ void check() {
 int main(int argc, char** argv) {
   const std::string mode = argc > 1 ? argv[1] : "check";
   if (mode == "layout") {
-    layout();
+    if (argc > 2 && std::string(argv[2]) == "corres")
+      layout_corres();
+    else
+      layout();
     return 0;
   }
   check();

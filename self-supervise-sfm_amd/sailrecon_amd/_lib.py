@@ -22,6 +22,7 @@ SR_EPI_BIAS, SR_EPI_BIAS_GELU, SR_EPI_BIAS_RESID, SR_EPI_QKV, SR_EPI_PATCH = 0, 
 SR_EPI_F32, SR_EPI_GELU_BWD = 5, 6
 SR_MASK_NONE, SR_MASK_CAMERA, SR_MASK_DENSE, SR_MASK_ADD = 0, 1, 2, 3
 SR_ATTN_MERGE_MAX_PARTS = 16
+SR_CORRES_F32, SR_CORRES_PNG16 = 0, 1
 
 _vp = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -124,6 +125,23 @@ class ImcLossDesc(ctypes.Structure):
     ]
 
 
+class CorresPair(ctypes.Structure):
+    """sr_corres_pair (include/sfm_amd.h): one record of the device-resident pair table."""
+    _fields_ = [
+        ("src", _vp), ("dst", _vp), ("dst_y", _vp), ("conf", _vp), ("depth_src", _vp), ("depth_dst", _vp),
+        ("format", _i32), ("m", _i32), ("hs", _i32), ("ws", _i32),
+        ("h1", _i32), ("w1", _i32), ("h2", _i32), ("w2", _i32),
+    ]
+
+
+class CorresDesc(ctypes.Structure):
+    _fields_ = [
+        ("n_pairs", _i32), ("n_points", _i32), ("pairs", _vp), ("max_m", _i32), ("uniforms", _vp),
+        ("min_conf", _f32), ("src_coords", _vp), ("dst_coords", _vp), ("src_depth", _vp), ("dst_depth", _vp),
+        ("index", _vp), ("total", _vp), ("n_valid", _vp), ("workspace", _vp), ("workspace_doubles", _i64),
+    ]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "sr_last_error": (ctypes.c_char_p, []),
@@ -210,6 +228,8 @@ _PROTOS = {
     "sr_imc_loss": (_i32, [_vp, ctypes.POINTER(ImcLossDesc)]),
     "sr_pose_act_bwd_f32": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32]),
     "sr_resize_crop_chw_f32": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "sr_corres_sample_workspace": (_i64, [_i32, _i32]),
+    "sr_corres_sample": (_i32, [_vp, ctypes.POINTER(CorresDesc)]),
 }
 EXPORTED = tuple(_PROTOS)
 

@@ -1119,6 +1119,109 @@ def resize_crop_chw(x: Tensor, size: int, top: int, left: int, out: Tensor, bicu
     check(rc, "sr_resize_crop_chw_f32")
 
 
+# ---------------------------------------------------------------- training correspondences (io.py:280-360)
+_CORRES_WS = {}  # (device, stream) -> fp64 workspace of sr_corres_sample
+
+
+def _corres_dev(t, name: str, dtypes, ndim: int) -> Tensor:
+    if not isinstance(t, Tensor) or not t.is_cuda:
+        raise ValueError(f"corres_sample: {name} must be a device tensor")
+    if t.dtype not in dtypes:
+        raise ValueError(f"corres_sample: {name} must be {' / '.join(str(d) for d in dtypes)}, got {t.dtype}")
+    if t.dim() != ndim or not t.is_contiguous() or t.numel() == 0:
+        raise ValueError(f"corres_sample: {name} must be a contiguous non-empty {ndim}-D tensor, got shape "
+                         f"{tuple(t.shape)} stride {t.stride()}")
+    return t
+
+
+def corres_sample(pairs, uniforms: Tensor, min_conf: float, *, want_index: bool = True, check: bool = True) -> dict:
+    """sample_correspondence_and_depth (train/utils/io.py:280-360) for every pair in one launch sequence
+    (sr_corres_sample).  ``pairs``: dicts of device tensors, each with depth_src [H1, W1] / depth_dst
+    [H2, W2] fp32 and either coords_src / coords_dst [M, 2] + certainty [M] fp32 or the matcher's
+    stored maps x_png / y_png / conf_png [hs, ws] (uint16, or its bits as int16); ``uniforms`` [P, K]
+    fp64 on the device.  Returns src_coords / dst_coords [P, K, 2], src_depth / dst_depth [P, K] fp32,
+    index [P, K] int32 (unfiltered numbering), total [P] fp64, n_valid [P] int32.  ``check`` reads
+    total / n_valid back (one synchronisation) and raises the reference's ValueError for a pair
+    with no correspondence above the threshold; every input is validated before any launch."""
+    if len(pairs) == 0:
+        raise ValueError("corres_sample: no pairs")
+    u = _corres_dev(uniforms, "uniforms", (torch.float64,), 2)
+    P, K = u.shape
+    if P != len(pairs):
+        raise ValueError(f"corres_sample: uniforms has {P} rows for {len(pairs)} pairs")
+    dev = u.device
+    u16 = (torch.uint16, torch.int16)
+    table = (_lib.CorresPair * P)()
+    max_m = 0
+    for j, pr in enumerate(pairs):
+        r = table[j]
+        ds = _corres_dev(pr["depth_src"], f"pair {j} depth_src", (torch.float32,), 2)
+        dd = _corres_dev(pr["depth_dst"], f"pair {j} depth_dst", (torch.float32,), 2)
+        if "x_png" in pr:
+            x, y, c = (_corres_dev(pr[k], f"pair {j} {k}", u16, 2) for k in ("x_png", "y_png", "conf_png"))
+            if x.shape != c.shape or y.shape != c.shape:
+                raise ValueError(f"corres_sample: pair {j} x_png {tuple(x.shape)}, y_png {tuple(y.shape)} and "
+                                 f"conf_png {tuple(c.shape)} differ in shape")
+            r.format, r.hs, r.ws, m = _lib.SR_CORRES_PNG16, c.shape[0], c.shape[1], c.numel()
+            r.src, r.dst, r.dst_y, r.conf = None, x.data_ptr(), y.data_ptr(), c.data_ptr()
+            used = (x, y, c)
+        else:
+            cs = _corres_dev(pr["coords_src"], f"pair {j} coords_src", (torch.float32,), 2)
+            cd = _corres_dev(pr["coords_dst"], f"pair {j} coords_dst", (torch.float32,), 2)
+            c = _corres_dev(pr["certainty"], f"pair {j} certainty", (torch.float32,), 1)
+            m = c.numel()
+            if cs.shape != (m, 2) or cd.shape != (m, 2):
+                raise ValueError(f"corres_sample: pair {j} coords_src {tuple(cs.shape)} / coords_dst {tuple(cd.shape)} "
+                                 f"do not match {m} certainties")
+            r.format, r.hs, r.ws = _lib.SR_CORRES_F32, 0, 0
+            r.src, r.dst, r.dst_y, r.conf = cs.data_ptr(), cd.data_ptr(), None, c.data_ptr()
+            used = (cs, cd, c)
+        if m >= 2 ** 31:
+            raise ValueError(f"corres_sample: pair {j} has {m} correspondences (int32 indices)")
+        for t in used + (ds, dd):
+            if t.device != dev:
+                raise ValueError(f"corres_sample: pair {j} tensors must live on {dev}")
+        r.m, r.depth_src, r.depth_dst = m, ds.data_ptr(), dd.data_ptr()
+        r.h1, r.w1, r.h2, r.w2 = ds.shape[0], ds.shape[1], dd.shape[0], dd.shape[1]
+        max_m = max(max_m, m)
+    # the pair table goes up in one pinned H2D copy
+    nbytes = ctypes.sizeof(table)
+    host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+    ctypes.memmove(host.data_ptr(), ctypes.addressof(table), nbytes)
+    table_dev = host.to(dev, non_blocking=True)
+    L = _lib.load()
+    need = L.sr_corres_sample_workspace(P, max_m)
+    key = _ws_stream_key(dev)
+    ws = _CORRES_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, device=dev, dtype=torch.float64)
+        _CORRES_WS[key] = ws
+    out = dict(src_coords=torch.empty(P, K, 2, device=dev), dst_coords=torch.empty(P, K, 2, device=dev),
+               src_depth=torch.empty(P, K, device=dev), dst_depth=torch.empty(P, K, device=dev),
+               index=torch.empty(P, K, device=dev, dtype=torch.int32) if want_index else None,
+               total=torch.empty(P, device=dev, dtype=torch.float64),
+               n_valid=torch.empty(P, device=dev, dtype=torch.int32))
+    d = _lib.CorresDesc()
+    d.n_pairs, d.n_points, d.pairs, d.max_m = P, K, _p(table_dev), max_m
+    d.uniforms, d.min_conf = _p(u), float(min_conf)
+    d.src_coords, d.dst_coords, d.src_depth, d.dst_depth = (_p(out[k]) for k in ("src_coords", "dst_coords",
+                                                                                   "src_depth", "dst_depth"))
+    d.index, d.total, d.n_valid = _p(out["index"]), _p(out["total"]), _p(out["n_valid"])
+    d.workspace, d.workspace_doubles = _p(ws), ws.numel()
+    _lib.check(L.sr_corres_sample(_stream(u), ctypes.byref(d)), "sr_corres_sample")
+    if check:
+        total, n_valid = out["total"].cpu(), out["n_valid"].cpu()
+        for j in range(P):
+            if int(n_valid[j]) < 0:
+                raise ValueError(f"corres_sample: pair {j}: the launch could not hold its record")
+            if not float(total[j]) > 0:
+                m = pairs[j]["conf_png"].numel() if "x_png" in pairs[j] else pairs[j]["certainty"].numel()
+                raise ValueError(f"Pair {j}: no correspondence points meet the minimum confidence threshold "
+                                 f"{min_conf}. Total points: {m}, points above threshold: {int(n_valid[j])}. "
+                                 f"Consider lowering min_corres_conf or checking correspondence quality.")
+    return out
+
+
 # ---------------------------------------------------------------- training step (SURVEY §8(f) rank 4)
 _TRAIN_WS = {}  # ((device, stream), name) -> fp32 workspace
 

@@ -268,3 +268,85 @@ class ImagePreprocessor:
         kp2k = torch.tensor([[1.0 / sx, 0.0, -ox / sx], [0.0, 1.0 / sy, -oy / sy], [0.0, 0.0, 1.0]],
                             dtype=torch.float32)
         return k2kp, kp2k
+
+
+# ---------------------------------------------------------------- correspondences (io.py:280-360)
+def _as_host(a, dtype: torch.dtype, what: str):
+    """numpy array / tensor -> tensor of ``dtype`` (uint16 maps travel as their int16 bits)."""
+    if isinstance(a, np.ndarray):
+        if dtype == torch.int16:
+            if a.dtype != np.uint16:
+                raise ValueError(f"{what} must be uint16 (got {a.dtype})")
+            return torch.from_numpy(np.ascontiguousarray(a).view(np.int16))
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dtype)
+    if not isinstance(a, Tensor):
+        raise TypeError(f"{what} must be a numpy array or a tensor (got {type(a).__name__})")
+    if dtype == torch.int16:
+        if a.dtype not in (torch.uint16, torch.int16):
+            raise ValueError(f"{what} must be uint16 (got {a.dtype})")
+        return a
+    return a.to(dtype)
+
+
+def _to_corres_device(t: Tensor, device) -> Tensor:
+    t = t.contiguous()
+    return t if t.is_cuda else runtime.to_device(t, device)
+
+
+def corres_entry(corr: Dict[str, Any], who: str) -> Dict[str, Tensor]:
+    """Validate one pair's correspondences on the host side: {coords_src, coords_dst, certainty}
+    ([M, 2] / [M, 2] / [M], any leading shape that flattens to it) or {x_png, y_png, conf_png}
+    ([hs, ws] uint16).  Returns tensors ready for upload."""
+    if "x_png" in corr:
+        x, y, c = (_as_host(corr[k], torch.int16, f"{who} {k}") for k in ("x_png", "y_png", "conf_png"))
+        if c.dim() != 2 or x.shape != c.shape or y.shape != c.shape or c.numel() == 0:
+            raise ValueError(f"{who}: x_png {tuple(x.shape)}, y_png {tuple(y.shape)} and conf_png {tuple(c.shape)} "
+                             f"must be equal non-empty [hs, ws] maps")
+        return dict(x_png=x, y_png=y, conf_png=c)
+    cs = _as_host(corr["coords_src"], torch.float32, f"{who} coords_src")
+    cd = _as_host(corr["coords_dst"], torch.float32, f"{who} coords_dst")
+    c = _as_host(corr["certainty"], torch.float32, f"{who} certainty").reshape(-1)
+    if cs.shape[-1:] != (2,) or cd.shape[-1:] != (2,):
+        raise ValueError(f"{who}: coords_src {tuple(cs.shape)} / coords_dst {tuple(cd.shape)} must end in 2")
+    cs, cd = cs.reshape(-1, 2), cd.reshape(-1, 2)
+    if c.numel() == 0 or cs.shape[0] != c.numel() or cd.shape[0] != c.numel():
+        raise ValueError(f"{who}: {cs.shape[0]} source coordinates, {cd.shape[0]} destination coordinates and "
+                         f"{c.numel()} certainties (mismatched lengths)")
+    return dict(coords_src=cs, coords_dst=cd, certainty=c)
+
+
+def depth_entry(depth, who: str) -> Tensor:
+    d = _as_host(depth, torch.float32, who)
+    if d.dim() != 2 or d.numel() == 0:
+        raise ValueError(f"{who} must be a non-empty [H, W] map (got {tuple(d.shape)})")
+    return d
+
+
+def corres_uniforms(uniforms, n_pairs: int, sample_num: int) -> Tensor:
+    """[P, K] fp64 host tensor: the caller's, or np.random.random_sample((P, K)) from numpy's global
+    state -- exactly what the reference's loop of np.random.choice calls consumes, pair after pair."""
+    if uniforms is None:
+        return torch.from_numpy(np.random.random_sample((n_pairs, sample_num)))
+    u = uniforms if isinstance(uniforms, Tensor) else torch.from_numpy(np.asarray(uniforms, dtype=np.float64))
+    if u.numel() != n_pairs * sample_num:
+        raise ValueError(f"uniforms must hold {n_pairs} x {sample_num} values (got {tuple(u.shape)})")
+    return u.to(torch.float64).reshape(n_pairs, sample_num)
+
+
+def sample_correspondence_and_depth(coords_src, coords_dst, certainty, depth_src, depth_dst, sample_num: int,
+                                    min_corres_conf: float = 0.0, *, uniforms=None, device="cuda"
+                                    ) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Mirror of train/utils/io.py:280-360 on the HIP path (sr_corres_sample): numpy arrays or tensors
+    in, device tensors out -- (coords_src_sampled [K, 2], coords_dst_sampled [K, 2] in pixels,
+    depth_src_sampled [K], depth_dst_sampled [K]).  ``uniforms`` ([K] fp64 in [0, 1)) replaces the
+    np.random.random_sample(K) draw from numpy's global state that np.random.choice makes."""
+    if int(sample_num) <= 0:
+        raise ValueError(f"sample_num must be positive (got {sample_num})")
+    e = corres_entry(dict(coords_src=coords_src, coords_dst=coords_dst, certainty=certainty), "correspondences")
+    ds, dd = depth_entry(depth_src, "depth_src"), depth_entry(depth_dst, "depth_dst")
+    u = corres_uniforms(uniforms, 1, int(sample_num))
+    dev = next((t.device for t in (*e.values(), ds, dd) if t.is_cuda), torch.device(device))
+    pair = {k: _to_corres_device(v, dev) for k, v in e.items()}
+    pair["depth_src"], pair["depth_dst"] = _to_corres_device(ds, dev), _to_corres_device(dd, dev)
+    out = ops.corres_sample([pair], _to_corres_device(u, dev), min_corres_conf, want_index=False)
+    return out["src_coords"][0], out["dst_coords"][0], out["src_depth"][0], out["dst_depth"][0]

@@ -650,6 +650,55 @@ def io():
     print(f"io Pillow on 1 host core: rgb {(t1 - t0) / 8 * 1e3:.2f} ms/view  depth {(t2 - t1) / 4 * 1e3:.2f} ms/view")
 
 
+def corres(P=240, hs=560, ws=560, K=10000, views=16, dh=768, dw=1024):
+    """Training correspondences and depths (sr_corres_sample; train/utils/io.py:280-360 per pair) at a
+    16-view scene's size: P ordered pairs of hs x ws matcher maps, K samples each, views depth maps
+    of dh x dw.  HIP-event time of the launch sequence for both input forms, the H2D time of each
+    form's inputs from pinned memory, and the achieved GB/s against the bytes the kernels must move
+    (scan: certainty in, fp64 CDF out; sample: uniforms in, six fp32 + one int32 out per point plus
+    the binary search's reads, counted as ceil(log2(chunks)) + ceil(log2(2048)) doubles)."""
+    import math
+    M = hs * ws
+    g = torch.Generator(device=DEV).manual_seed(0)
+    depths = [1 + 4 * torch.rand(dh, dw, device=DEV, generator=g) for _ in range(views)]
+    order = [(a, b) for a in range(views) for b in range(views) if a != b][:P]
+    png, f32 = [], []
+    for _ in range(P):
+        t = torch.randint(0, 65536, (3, hs, ws), device=DEV, generator=g, dtype=torch.int32)
+        t[2] %= 1001
+        png.append((t - 65536 * (t >= 32768)).to(torch.int16))  # the uint16 bits
+        v = t.float()
+        f32.append((torch.rand(M, 2, device=DEV, generator=g) * 2 - 1,
+                    torch.stack([v[0] / 65535.0 * 2 - 1, v[1] / 65535.0 * 2 - 1], -1).reshape(M, 2).contiguous(),
+                    (v[2] / 1000).reshape(M).contiguous()))
+    u = torch.rand(P, K, device=DEV, dtype=torch.float64, generator=g)
+    recs_png = [dict(x_png=t[0], y_png=t[1], conf_png=t[2], depth_src=depths[a], depth_dst=depths[b])
+                for t, (a, b) in zip(png, order)]
+    recs_f32 = [dict(coords_src=c[0], coords_dst=c[1], certainty=c[2], depth_src=depths[a], depth_dst=depths[b])
+                for c, (a, b) in zip(f32, order)]
+    steps = math.ceil(math.log2(max(2, math.ceil(M / 2048)))) + 11
+    out_bytes = P * K * (8 + 8 * steps + 6 * 4 + 4)
+    for name, recs, esz in (("f32  ", recs_f32, 4), ("png16", recs_png, 2)):
+        ms = timeit(lambda: ops.corres_sample(recs, u, 0.1, check=False), reps=200, warm=3)
+        t0 = time.perf_counter()
+        ops.corres_sample(recs, u, 0.1)
+        wall = (time.perf_counter() - t0) * 1e3
+        moved = P * M * (esz + 8) + out_bytes
+        print(f"corres {name} P {P} M {M} K {K}: launch sequence {ms:8.3f} ms  ({ms / P * 1e3:.1f} us/pair)  "
+              f"{moved / ms / 1e6:7.1f} GB/s of {moved / 1e6:.0f} MB   call incl. table + readback {wall:.2f} ms",
+              flush=True)
+    for name, tensors in (("f32  ", [t for c in f32 for t in c]), ("png16", png)):
+        host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t) for t in tensors]
+        dst = [torch.empty_like(t) for t in tensors]
+        nbytes = sum(t.numel() * t.element_size() for t in tensors)
+        ms = timeit(lambda: [d.copy_(h, non_blocking=True) for d, h in zip(dst, host)], reps=10, warm=1)
+        print(f"corres {name} H2D of the correspondence inputs (pinned): {ms:8.2f} ms  {nbytes / 1e6:.0f} MB  "
+              f"{nbytes / ms / 1e6:.1f} GB/s", flush=True)
+        del host, dst
+    nd = views * dh * dw * 4
+    print(f"corres depth maps: {nd / 1e6:.0f} MB for {views} views (resident: ImagePreprocessor's output)")
+
+
 def attn_fp8():
     """Global attention with q.k^T in block-scaled fp8 (BASELINE C5) vs the bf16 kernel, at the
     C3 (L = 43,968) and C5 (L = 175,872) global lengths; the fp8 time includes both quantisations."""
