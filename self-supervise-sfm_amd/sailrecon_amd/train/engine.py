@@ -27,6 +27,7 @@ from __future__ import annotations
 
 import os
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Callable, Optional
 
 import torch
@@ -75,69 +76,66 @@ def alloc_tape(rows: int, dim: int, hidden: int, dtype: torch.dtype, device, lse
                      xn2=e(rows, dim), u=e(rows, hidden), h=e(rows, hidden))
 
 
+def _gemm_stage(probs, epi: int, tag: str) -> None:
+    """One GEMM stage of every item (dicts: a, w, out and ops.gemm's keywords): ONE grouped launch
+    (sr_gemm_group) for several eligible problems, else ops.gemm each.  One problem never groups:
+    ops.gemm picks its kernel and the split-K of few rows (the fp32 camera trunk)."""
+    if len(probs) > 1 and ops.gemm_group_eligible(probs):
+        ops.gemm_group(probs, epi, tag=tag)
+        return
+    for q in probs:
+        ops.gemm(q["a"], q["w"], q["out"], epi, tag=tag, **{k: v for k, v in q.items() if k not in ("a", "w", "out")})
+
+
+def _one_by_one(items, same_epi: bool) -> bool:
+    """Whether several items cannot share stages: not all bf16, (C, hidden) differ or (forward) only
+    some have a qk-norm / RoPE epilogue."""
+    return len(items) > 1 and (
+        not all(it["tape"].xn1.dtype == torch.bfloat16 for it in items) or
+        len({(it["tape"].xn1.shape[1], it["tape"].u.shape[1]) for it in items}) != 1 or
+        (same_epi and len({it["qkv_epi"] is None for it in items}) != 1))
+
+
 def run_block_train(pb: runtime.PackedBlock, x: Tensor, r0: int, r1: int, tape: BlockTape,
                     attend: Callable[[Tensor, Tensor, Optional[Tensor]], None], qkv_epi: Optional[dict]) -> None:
     """x[r0:r1] <- Block(x[r0:r1]) keeping the backward's inputs in ``tape``."""
-    xs = x[r0:r1]
-    ops.layernorm(xs, pb.ln1_w, pb.ln1_b, pb.eps, tape.xn1, x_copy=tape.x0)  # x0 = x in the same pass
-    if qkv_epi is None:
-        ops.gemm(tape.xn1, pb.w_qkv, tape.qkv, _lib.SR_EPI_BIAS, bias=pb.b_qkv, tag="gemm")
-    else:
-        ops.gemm(tape.xn1, pb.w_qkv, tape.qkv, _lib.SR_EPI_QKV, bias=pb.b_qkv, qkv=qkv_epi, aux=tape.raw, tag="gemm")
-    attend(tape.qkv, tape.o, tape.lse)
-    ops.gemm(tape.o, pb.w_proj, xs, _lib.SR_EPI_BIAS_RESID, bias=pb.b_proj, gamma=pb.g1, tag="gemm")
-    ops.layernorm(xs, pb.ln2_w, pb.ln2_b, pb.eps, tape.xn2, x_copy=tape.x1)  # x1 = x likewise
-    ops.gemm(tape.xn2, pb.w_fc1, tape.h, _lib.SR_EPI_BIAS_GELU, bias=pb.b_fc1, aux=tape.u, tag="gemm")
-    ops.gemm(tape.h, pb.w_fc2, xs, _lib.SR_EPI_BIAS_RESID, bias=pb.b_fc2, gamma=pb.g2, tag="gemm")
+    run_block_train_multi([dict(pb=pb, x=x, r0=r0, r1=r1, tape=tape, attend=attend, qkv_epi=qkv_epi)])
 
 
 def run_block_train_multi(items) -> None:
     """run_block_train for several independent block applications of equal width at once (the
     layer's reloc and global blocks: different weights, disjoint rows of x, the reloc block's
-    anchor K|V already projected): stage by stage in run_block_train's order, each GEMM of all
-    items as ONE grouped launch (sr_gemm_group) whose last partial round the items share.  At C4
-    each item's N = 1,024 GEMMs (proj, fc2) are 344 tiles of 256^2, which sr_gemm alone runs on
-    the 128^2 kernel; grouped they run on the 256^2 kernel, whose results differ from it by fp32
-    accumulation order only (gemm_resid 41.7 -> 38.9 ms per C4 step, profiles/r05_j29_*).  fc1
-    stays one launch per item.  ``items``: dicts of run_block_train's arguments (pb, x, r0, r1,
-    tape, attend, qkv_epi); their attentions run in list order."""
-    if len(items) == 1 or not all(it["tape"].xn1.dtype == torch.bfloat16 for it in items) or \
-            len({(it["pb"].dim, it["tape"].u.shape[1]) for it in items}) != 1 or \
-            len({it["qkv_epi"] is None for it in items}) != 1:
+    anchor K|V already projected): stage by stage, each GEMM of all items as ONE grouped launch
+    (sr_gemm_group) whose last partial round the items share.  At C4 each item's N = 1,024 GEMMs
+    (proj, fc2) are 344 tiles of 256^2, which sr_gemm alone runs on the 128^2 kernel; grouped they
+    run on the 256^2 kernel, whose results differ from it by fp32 accumulation order only
+    (gemm_resid 41.7 -> 38.9 ms per C4 step, profiles/r05_j29_*).  fc1 stays one launch per item.
+    ``items``: dicts of run_block_train's arguments (pb, x, r0, r1, tape, attend, qkv_epi), not
+    modified; their attentions run in list order.  Items of mixed dtype, width or qkv epilogue run
+    one after another."""
+    if _one_by_one(items, same_epi=True):
         for it in items:
-            run_block_train(it["pb"], it["x"], it["r0"], it["r1"], it["tape"], it["attend"], it["qkv_epi"])
+            run_block_train_multi([it])
         return
-
-    def group(epi, probs):
-        if ops.gemm_group_eligible(probs):
-            ops.gemm_group(probs, epi, tag="gemm")
-        else:
-            for q in probs:
-                ops.gemm(q["a"], q["w"], q["out"], epi, bias=q.get("bias"), gamma=q.get("gamma"), qkv=q.get("qkv"),
-                         aux=q.get("aux"), tag="gemm")
-
-    for it in items:
-        it["_xs"] = it["x"][it["r0"]:it["r1"]]
-        ops.layernorm(it["_xs"], it["pb"].ln1_w, it["pb"].ln1_b, it["pb"].eps, it["tape"].xn1, x_copy=it["tape"].x0)
-    if items[0]["qkv_epi"] is None:
-        group(_lib.SR_EPI_BIAS, [dict(a=it["tape"].xn1, w=it["pb"].w_qkv, out=it["tape"].qkv, bias=it["pb"].b_qkv)
-                                 for it in items])
+    its = [SimpleNamespace(**it, xs=it["x"][it["r0"]:it["r1"]]) for it in items]
+    for s in its:
+        ops.layernorm(s.xs, s.pb.ln1_w, s.pb.ln1_b, s.pb.eps, s.tape.xn1, x_copy=s.tape.x0)  # x0 = x in the same pass
+    if its[0].qkv_epi is None:
+        _gemm_stage([dict(a=s.tape.xn1, w=s.pb.w_qkv, out=s.tape.qkv, bias=s.pb.b_qkv) for s in its],
+                    _lib.SR_EPI_BIAS, "gemm")
     else:
-        group(_lib.SR_EPI_QKV, [dict(a=it["tape"].xn1, w=it["pb"].w_qkv, out=it["tape"].qkv, bias=it["pb"].b_qkv,
-                                     qkv=it["qkv_epi"], aux=it["tape"].raw) for it in items])
-    for it in items:
-        it["attend"](it["tape"].qkv, it["tape"].o, it["tape"].lse)
-    group(_lib.SR_EPI_BIAS_RESID, [dict(a=it["tape"].o, w=it["pb"].w_proj, out=it["_xs"], bias=it["pb"].b_proj,
-                                        gamma=it["pb"].g1) for it in items])
-    for it in items:
-        ops.layernorm(it["_xs"], it["pb"].ln2_w, it["pb"].ln2_b, it["pb"].eps, it["tape"].xn2, x_copy=it["tape"].x1)
-    for it in items:  # fc1 apart: sr_gemm's tail split beats the group here (35.5 vs 34.9 ms/step, j29)
-        ops.gemm(it["tape"].xn2, it["pb"].w_fc1, it["tape"].h, _lib.SR_EPI_BIAS_GELU, bias=it["pb"].b_fc1,
-                 aux=it["tape"].u, tag="gemm")
-    group(_lib.SR_EPI_BIAS_RESID, [dict(a=it["tape"].h, w=it["pb"].w_fc2, out=it["_xs"], bias=it["pb"].b_fc2,
-                                        gamma=it["pb"].g2) for it in items])
-    for it in items:
-        it.pop("_xs")
+        _gemm_stage([dict(a=s.tape.xn1, w=s.pb.w_qkv, out=s.tape.qkv, bias=s.pb.b_qkv, qkv=s.qkv_epi, aux=s.tape.raw)
+                     for s in its], _lib.SR_EPI_QKV, "gemm")
+    for s in its:
+        s.attend(s.tape.qkv, s.tape.o, s.tape.lse)
+    _gemm_stage([dict(a=s.tape.o, w=s.pb.w_proj, out=s.xs, bias=s.pb.b_proj, gamma=s.pb.g1) for s in its],
+                _lib.SR_EPI_BIAS_RESID, "gemm")
+    for s in its:
+        ops.layernorm(s.xs, s.pb.ln2_w, s.pb.ln2_b, s.pb.eps, s.tape.xn2, x_copy=s.tape.x1)  # x1 = x likewise
+    for s in its:  # fc1 apart: sr_gemm's tail split beats the group here (35.5 vs 34.9 ms/step, j29)
+        ops.gemm(s.tape.xn2, s.pb.w_fc1, s.tape.h, _lib.SR_EPI_BIAS_GELU, bias=s.pb.b_fc1, aux=s.tape.u, tag="gemm")
+    _gemm_stage([dict(a=s.tape.h, w=s.pb.w_fc2, out=s.xs, bias=s.pb.b_fc2, gamma=s.pb.g2) for s in its],
+                _lib.SR_EPI_BIAS_RESID, "gemm")
 
 
 # ----------------------------------------------------------------------------- parameters
@@ -236,14 +234,8 @@ def refresh_block_bf16(blk, pb: runtime.PackedBlock, into: BwdPack) -> None:
     ops.weight_refresh(refresh_items_bf16(blk, pb, into))
 
 
-class BwdScratch:
+class BwdScratch(runtime.Workspace):
     """Grow-only backward scratch shared by every block of one stream."""
-
-    def __init__(self):
-        self.ws = runtime.Workspace()
-
-    def get(self, name, rows, cols, dtype, device):
-        return self.ws.get(name, rows, cols, dtype, device)
 
 
 def _resid_wants_sum(bias: Optional[Tensor], g_bias: Optional[Tensor], g_gamma: Optional[Tensor]) -> bool:
@@ -269,6 +261,29 @@ def _resid_param_grads(dx: Tensor, bias: Optional[Tensor], gamma: Optional[Tenso
         ops.vec_fma(pairs[0][0], pairs[0][1], tmp)
 
 
+def _wgrad_stage(args, bf: bool, tag: str) -> None:
+    """One weight-gradient stage of every item: (item tag, dy, x, dw, db, rowscale, wdot, rowdot)
+    each.  bf16: sr_gemm_wgrad (+ db from a column sum of dy); two items of one weight shape share
+    ONE launch (sr_gemm_wgrad_pair) where ops.wgrad_pair_splits says it pays.  fp32: the small-row
+    kernel with db folded in."""
+    if not bf:
+        for _, dy, x, dw, db, rowscale, wdot, rowdot in args:
+            ops.wgrad_small(dy, x, dw, db=db, accumulate=True, rowscale=rowscale, wdot=wdot, rowdot=rowdot)
+        return
+    sp = None
+    if _PAIR_WGRAD and len(args) == 2 and args[0][3].shape == args[1][3].shape:
+        sp = ops.wgrad_pair_splits(args[0][1].shape[0], args[1][1].shape[0], *args[0][3].shape)
+    if sp is not None:
+        ops.gemm_wgrad_pair([dict(dy=a[1], x=a[2], dw=a[3], accumulate=True, rowscale=a[5], wdot=a[6], rowdot=a[7])
+                             for a in args], sp, tag=tag + ".wgrad")
+    for item_tag, dy, x, dw, db, rowscale, wdot, rowdot in args:
+        if sp is None:
+            ops.gemm_wgrad(dy, x, dw, accumulate=True, rowscale=rowscale, wdot=wdot, rowdot=rowdot,
+                           tag=item_tag + ".wgrad")
+        if db is not None:
+            ops.colsum(dy, db, accumulate=True)
+
+
 def block_bwd(pb: runtime.PackedBlock, bp: BwdPack, g: BlockGrads, tape: BlockTape, dx: Tensor,
               dxb: Optional[Tensor], attend_bwd: Callable[[BlockTape, Tensor, Tensor], None],
               qkv_epi: Optional[dict], sc: BwdScratch, tag: str = "bwd") -> None:
@@ -276,162 +291,79 @@ def block_bwd(pb: runtime.PackedBlock, bp: BwdPack, g: BlockGrads, tape: BlockTa
     (bf16 copy of dx, bf16 blocks) refreshed alongside; parameter grads accumulated.
     ``attend_bwd(tape, dO, dqkv)`` writes fp32 dq|dk|dv into dqkv [R, 3C] (and any shared-segment
     grads elsewhere)."""
-    R, C = dx.shape
-    Hd = tape.u.shape[1]
-    dev = dx.device
-    dt = tape.xn1.dtype
-    bf = dt == torch.bfloat16
-    a_op = dxb if bf else dx   # GEMM operand view of dx
-    tmp = sc.get("colsum_tmp", 1, max(C, Hd, 3 * C), torch.float32, dev)[0]
-
-    def wgrad(dy, x, dw, db=None, rowscale=None, wdot=None, rowdot=None):
-        if bf:
-            ops.gemm_wgrad(dy, x, dw, accumulate=True, rowscale=rowscale, wdot=wdot, rowdot=rowdot, tag=tag + ".wgrad")
-            if db is not None:
-                ops.colsum(dy, db, accumulate=True)
-        else:
-            ops.wgrad_small(dy, x, dw, db=db, accumulate=True, rowscale=rowscale, wdot=wdot, rowdot=rowdot)
-
-    # ---- MLP: x2 = x1 + g2 * fc2(GELU(fc1(LN2(x1))))
-    dU = sc.get("dU", R, Hd, dt, dev)
-    # bf16: fc1's bias grad from the GELU_BWD epilogue's per-64-row column sums (no re-read of dU)
-    csU = (sc.get("dU_colsum", ops.colsum_blocks(R), Hd, torch.float32, dev)
-           if bf and g.b_fc1 is not None and GELU_COLSUM else None)
-    ops.gemm(a_op, bp.wt_fc2, dU, _lib.SR_EPI_GELU_BWD, aux=tape.u, colsum=csU, tag=tag + ".dgrad")
-    wgrad(a_op, tape.h, g.w_fc2, rowscale=pb.g2, wdot=bp.w_fc2 if g.g2 is not None else None,
-          rowdot=g.g2 if g.g2 is not None else None)
-    _resid_param_grads(dx, bp.b_fc2, pb.g2, g.b_fc2, g.g2, tmp[:C])
-    dxn = sc.get("dxn", R, C, torch.float32, dev)
-    ops.gemm(dU, bp.wt_fc1, dxn, _lib.SR_EPI_F32, tag=tag + ".dgrad")
-    wgrad(dU, tape.xn2, g.w_fc1, db=None if csU is not None else g.b_fc1)
-    if csU is not None:
-        ops.colsum(csU, g.b_fc1, accumulate=True)
-    # (LN2's backward also sums the updated dx over the rows: proj's bias / gamma grads below)
-    fused_sum = g.ln2_w is not None and C <= 2048 and _resid_wants_sum(bp.b_proj, g.b_proj, g.g1)
-    ops.layernorm_bwd(tape.x1, dxn, pb.ln2_w, pb.eps, dx, dxb=dxb, dw=g.ln2_w, db=g.ln2_b,
-                      dx_sum=tmp[:C] if fused_sum else None)
-
-    # ---- attention: x1 = x0 + g1 * proj(attn(qk(qkv(LN1(x0)))))
-    dO = sc.get("dO", R, C, dt, dev)
-    ops.gemm(a_op, bp.wt_proj, dO, _lib.SR_EPI_BIAS, tag=tag + ".dgrad")
-    wgrad(a_op, tape.o, g.w_proj, rowscale=pb.g1, wdot=bp.w_proj if g.g1 is not None else None,
-          rowdot=g.g1 if g.g1 is not None else None)
-    _resid_param_grads(dx, bp.b_proj, pb.g1, g.b_proj, g.g1, tmp[:C], summed=fused_sum)
-    dqkv = sc.get("dqkv", R, 3 * C, torch.float32, dev)
-    attend_bwd(tape, dO, dqkv)
-    if bf:  # (+ the qkv bias grad from the same pass: no bf16 column sum of draw afterwards)
-        draw = sc.get("draw", R, 3 * C, dt, dev)
-        ops.qk_bwd(tape.raw if qkv_epi is not None else None, dqkv, draw, qkv_epi or dict(embed_dim=C, head_dim=64),
-                   grads=g.qkn, bias_grad=g.b_qkv if QK_COLSUM else None)
-    elif qkv_epi is not None:  # fp32 block (autocast off) with qk-norm / RoPE: in place on dqkv
-        ops.qk_bwd(tape.raw, dqkv, dqkv, qkv_epi, grads=g.qkn)
-        draw = dqkv
-    else:
-        draw = dqkv
-    ops.gemm(draw, bp.wt_qkv, dxn, _lib.SR_EPI_F32, tag=tag + ".dgrad")
-    wgrad(draw, tape.xn1, g.w_qkv, db=None if bf and QK_COLSUM else g.b_qkv)
-    ops.layernorm_bwd(tape.x0, dxn, pb.ln1_w, pb.eps, dx, dxb=dxb, dw=g.ln1_w, db=g.ln1_b)
+    block_bwd_multi([dict(pb=pb, bp=bp, g=g, tape=tape, dx=dx, dxb=dxb, attend_bwd=attend_bwd, qkv_epi=qkv_epi,
+                          sc=sc, tag=tag)])
 
 
 def block_bwd_multi(items, tag: str = "pair") -> None:
     """block_bwd for several independent block applications of equal width at once (the layer's
-    reloc and global blocks: different weights, disjoint rows): stage by stage in block_bwd's
-    order, each stage's dgrad GEMMs of all items as ONE grouped launch (sr_gemm_group), whose
-    last partial round of workgroups the items share (at C4 each item's N = 1,024 dgrads are
-    344 tiles of 256^2, 1.3 rounds alone).  ``items``: dicts of block_bwd's arguments (pb, bp, g,
-    tape, dx, dxb, attend_bwd, qkv_epi, sc, tag); their attention backwards run in list order.
+    reloc and global blocks: different weights, disjoint rows): stage by stage, each stage's
+    dgrad GEMMs of all items as ONE grouped launch (sr_gemm_group), whose last partial round of
+    workgroups the items share (at C4 each item's N = 1,024 dgrads are 344 tiles of 256^2, 1.3
+    rounds alone).  ``items``: dicts of block_bwd's arguments (pb, bp, g, tape, dx, dxb,
+    attend_bwd, qkv_epi, sc, tag), not modified; their attention backwards run in list order.
     A grouped product runs on the 256^2 kernel with sr_gemm's per-tile order; where sr_gemm
-    alone would have picked the 128^2 kernel the results differ by fp32 accumulation order."""
-    if len(items) == 1 or not all(it["tape"].xn1.dtype == torch.bfloat16 for it in items) or \
-            len({(it["dx"].shape[1], it["tape"].u.shape[1]) for it in items}) != 1:
+    alone would have picked the 128^2 kernel the results differ by fp32 accumulation order.
+    Timer tags: ``tag`` on what the items share (dgrads, paired weight grads), the item's own on its
+    other weight grads, and on everything of an item that runs alone (mixed dtypes or widths)."""
+    if _one_by_one(items, same_epi=False):
         for it in items:
-            block_bwd(it["pb"], it["bp"], it["g"], it["tape"], it["dx"], it["dxb"], it["attend_bwd"], it["qkv_epi"],
-                      it["sc"], tag=it["tag"])
+            block_bwd_multi([it])
         return
-    C = items[0]["dx"].shape[1]
-    Hd = items[0]["tape"].u.shape[1]
-    dev = items[0]["dx"].device
-    dt = torch.bfloat16
-
-    def dgrad(epi, probs):
-        if ops.gemm_group_eligible(probs):
-            ops.gemm_group(probs, epi, tag=tag + ".dgrad")
-        else:
-            for q in probs:
-                ops.gemm(q["a"], q["w"], q["out"], epi, aux=q.get("aux"), colsum=q.get("colsum"), tag=tag + ".dgrad")
-
-    def wgrad(it, dy, x, dw, db=None, rowscale=None, wdot=None, rowdot=None):
-        ops.gemm_wgrad(dy, x, dw, accumulate=True, rowscale=rowscale, wdot=wdot, rowdot=rowdot,
-                       tag=it["tag"] + ".wgrad")
-        if db is not None:
-            ops.colsum(dy, db, accumulate=True)
-
-    def wgrads(args):
-        """One stage's weight grads of every item: (it, dy, x, dw, db, rowscale, wdot, rowdot) each;
-        two items of one weight shape share one launch where ops.wgrad_pair_splits says it pays."""
-        sp = None
-        if _PAIR_WGRAD and len(args) == 2 and args[0][3].shape == args[1][3].shape:
-            sp = ops.wgrad_pair_splits(args[0][1].shape[0], args[1][1].shape[0], *args[0][3].shape)
-        if sp is None:
-            for a in args:
-                wgrad(*a)
-            return
-        ops.gemm_wgrad_pair([dict(dy=a[1], x=a[2], dw=a[3], accumulate=True, rowscale=a[5], wdot=a[6], rowdot=a[7])
-                             for a in args], sp, tag=tag + ".wgrad")
-        for a in args:
-            if a[4] is not None:
-                ops.colsum(a[1], a[4], accumulate=True)
-
-    for it in items:
-        R = it["dx"].shape[0]
-        it["_tmp"] = it["sc"].get("colsum_tmp", 1, max(C, Hd, 3 * C), torch.float32, dev)[0]
-        it["_dU"] = it["sc"].get("dU", R, Hd, dt, dev)
-        it["_csU"] = (it["sc"].get("dU_colsum", ops.colsum_blocks(R), Hd, torch.float32, dev)
-                      if it["g"].b_fc1 is not None and GELU_COLSUM else None)
-        it["_dxn"] = it["sc"].get("dxn", R, C, torch.float32, dev)
-        it["_dO"] = it["sc"].get("dO", R, C, dt, dev)
+    if len(items) == 1:
+        tag = items[0]["tag"]
+    C, Hd = items[0]["dx"].shape[1], items[0]["tape"].u.shape[1]
+    dev, dt = items[0]["dx"].device, items[0]["tape"].xn1.dtype
+    bf = dt == torch.bfloat16
+    its = [SimpleNamespace(**it) for it in items]
+    for s in its:
+        s.R = s.dx.shape[0]
+        s.a = s.dxb if bf else s.dx   # GEMM operand view of dx
+        s.tmp = s.sc.get("colsum_tmp", 1, max(C, Hd, 3 * C), torch.float32, dev)[0]
+        s.dU = s.sc.get("dU", s.R, Hd, dt, dev)
+        # bf16: fc1's bias grad from the GELU_BWD epilogue's per-64-row column sums (no re-read of dU)
+        s.csU = (s.sc.get("dU_colsum", ops.colsum_blocks(s.R), Hd, torch.float32, dev)
+                 if bf and s.g.b_fc1 is not None and GELU_COLSUM else None)
+        s.dxn = s.sc.get("dxn", s.R, C, torch.float32, dev)
+        s.dO = s.sc.get("dO", s.R, C, dt, dev)
     # ---- MLP: x2 = x1 + g2 * fc2(GELU(fc1(LN2(x1))))
-    dgrad(_lib.SR_EPI_GELU_BWD, [dict(a=it["dxb"], w=it["bp"].wt_fc2, out=it["_dU"], aux=it["tape"].u,
-                                      colsum=it["_csU"]) for it in items])
-    wgrads([(it, it["dxb"], it["tape"].h, it["g"].w_fc2, None, it["pb"].g2,
-             it["bp"].w_fc2 if it["g"].g2 is not None else None, it["g"].g2) for it in items])
-    for it in items:
-        pb, bp, g = it["pb"], it["bp"], it["g"]
-        _resid_param_grads(it["dx"], bp.b_fc2, pb.g2, g.b_fc2, g.g2, it["_tmp"][:C])
-    dgrad(_lib.SR_EPI_F32, [dict(a=it["_dU"], w=it["bp"].wt_fc1, out=it["_dxn"]) for it in items])
-    wgrads([(it, it["_dU"], it["tape"].xn2, it["g"].w_fc1, None if it["_csU"] is not None else it["g"].b_fc1,
-             None, None, None) for it in items])
-    for it in items:  # fc1's bias grads from the GELU_BWD epilogue's column sums
-        if it["_csU"] is not None:
-            ops.colsum(it["_csU"], it["g"].b_fc1, accumulate=True)
-    for it in items:
-        pb, bp, g = it["pb"], it["bp"], it["g"]
-        it["_fused"] = g.ln2_w is not None and C <= 2048 and _resid_wants_sum(bp.b_proj, g.b_proj, g.g1)
-        ops.layernorm_bwd(it["tape"].x1, it["_dxn"], pb.ln2_w, pb.eps, it["dx"], dxb=it["dxb"], dw=g.ln2_w,
-                          db=g.ln2_b, dx_sum=it["_tmp"][:C] if it["_fused"] else None)
+    _gemm_stage([dict(a=s.a, w=s.bp.wt_fc2, out=s.dU, aux=s.tape.u, colsum=s.csU) for s in its],
+                _lib.SR_EPI_GELU_BWD, tag + ".dgrad")
+    _wgrad_stage([(s.tag, s.a, s.tape.h, s.g.w_fc2, None, s.pb.g2, s.bp.w_fc2 if s.g.g2 is not None else None, s.g.g2)
+                  for s in its], bf, tag)
+    for s in its:
+        _resid_param_grads(s.dx, s.bp.b_fc2, s.pb.g2, s.g.b_fc2, s.g.g2, s.tmp[:C])
+    _gemm_stage([dict(a=s.dU, w=s.bp.wt_fc1, out=s.dxn) for s in its], _lib.SR_EPI_F32, tag + ".dgrad")
+    _wgrad_stage([(s.tag, s.dU, s.tape.xn2, s.g.w_fc1, None if s.csU is not None else s.g.b_fc1, None, None, None)
+                  for s in its], bf, tag)
+    for s in its:
+        if s.csU is not None:
+            ops.colsum(s.csU, s.g.b_fc1, accumulate=True)
+    for s in its:  # (LN2's backward also sums the updated dx over the rows: proj's bias / gamma grads below)
+        s.fused_sum = s.g.ln2_w is not None and C <= 2048 and _resid_wants_sum(s.bp.b_proj, s.g.b_proj, s.g.g1)
+        ops.layernorm_bwd(s.tape.x1, s.dxn, s.pb.ln2_w, s.pb.eps, s.dx, dxb=s.dxb, dw=s.g.ln2_w, db=s.g.ln2_b,
+                          dx_sum=s.tmp[:C] if s.fused_sum else None)
     # ---- attention: x1 = x0 + g1 * proj(attn(qk(qkv(LN1(x0)))))
-    dgrad(_lib.SR_EPI_BIAS, [dict(a=it["dxb"], w=it["bp"].wt_proj, out=it["_dO"]) for it in items])
-    wgrads([(it, it["dxb"], it["tape"].o, it["g"].w_proj, None, it["pb"].g1,
-             it["bp"].w_proj if it["g"].g1 is not None else None, it["g"].g1) for it in items])
-    for it in items:
-        pb, bp, g = it["pb"], it["bp"], it["g"]
-        _resid_param_grads(it["dx"], bp.b_proj, pb.g1, g.b_proj, g.g1, it["_tmp"][:C], summed=it["_fused"])
-    for it in items:
-        R = it["dx"].shape[0]
-        dqkv = it["sc"].get("dqkv", R, 3 * C, torch.float32, dev)
-        it["attend_bwd"](it["tape"], it["_dO"], dqkv)
-        it["_draw"] = it["sc"].get("draw", R, 3 * C, dt, dev)
-        qkv_epi = it["qkv_epi"]
-        ops.qk_bwd(it["tape"].raw if qkv_epi is not None else None, dqkv, it["_draw"],
-                   qkv_epi or dict(embed_dim=C, head_dim=64), grads=it["g"].qkn,
-                   bias_grad=it["g"].b_qkv if QK_COLSUM else None)
-    dgrad(_lib.SR_EPI_F32, [dict(a=it["_draw"], w=it["bp"].wt_qkv, out=it["_dxn"]) for it in items])
-    wgrads([(it, it["_draw"], it["tape"].xn1, it["g"].w_qkv, None if QK_COLSUM else it["g"].b_qkv, None, None, None)
-            for it in items])
-    for it in items:
-        pb, g = it["pb"], it["g"]
-        ops.layernorm_bwd(it["tape"].x0, it["_dxn"], pb.ln1_w, pb.eps, it["dx"], dxb=it["dxb"], dw=g.ln1_w,
-                          db=g.ln1_b)
+    _gemm_stage([dict(a=s.a, w=s.bp.wt_proj, out=s.dO) for s in its], _lib.SR_EPI_BIAS, tag + ".dgrad")
+    _wgrad_stage([(s.tag, s.a, s.tape.o, s.g.w_proj, None, s.pb.g1, s.bp.w_proj if s.g.g1 is not None else None, s.g.g1)
+                  for s in its], bf, tag)
+    for s in its:
+        _resid_param_grads(s.dx, s.bp.b_proj, s.pb.g1, s.g.b_proj, s.g.g1, s.tmp[:C], summed=s.fused_sum)
+    for s in its:
+        s.draw = dqkv = s.sc.get("dqkv", s.R, 3 * C, torch.float32, dev)
+        s.attend_bwd(s.tape, s.dO, dqkv)
+        if bf:  # (+ the qkv bias grad from the same pass: no bf16 column sum of draw afterwards)
+            s.draw = s.sc.get("draw", s.R, 3 * C, dt, dev)
+            ops.qk_bwd(s.tape.raw if s.qkv_epi is not None else None, dqkv, s.draw,
+                       s.qkv_epi or dict(embed_dim=C, head_dim=64), grads=s.g.qkn,
+                       bias_grad=s.g.b_qkv if QK_COLSUM else None)
+        elif s.qkv_epi is not None:  # fp32 block (autocast off) with qk-norm / RoPE: in place on dqkv
+            ops.qk_bwd(s.tape.raw, dqkv, dqkv, s.qkv_epi, grads=s.g.qkn)
+    _gemm_stage([dict(a=s.draw, w=s.bp.wt_qkv, out=s.dxn) for s in its], _lib.SR_EPI_F32, tag + ".dgrad")
+    _wgrad_stage([(s.tag, s.draw, s.tape.xn1, s.g.w_qkv, None if bf and QK_COLSUM else s.g.b_qkv, None, None, None)
+                  for s in its], bf, tag)
+    for s in its:
+        ops.layernorm_bwd(s.tape.x0, s.dxn, s.pb.ln1_w, s.pb.eps, s.dx, dxb=s.dxb, dw=s.g.ln1_w, db=s.g.ln1_b)
 
 
 def frame_attend_train(pb: runtime.PackedBlock, frames: int, tokens: int):

@@ -276,8 +276,7 @@ class TrainGraph:
                 engine.run_block_train_multi([rel, glo])
             else:
                 for it in (rel, glo):
-                    engine.run_block_train(it["pb"], it["x"], it["r0"], it["r1"], it["tape"], it["attend"],
-                                           it["qkv_epi"])
+                    engine.run_block_train_multi([it])
             if l == agg.depth - 1:
                 ops.copy_rows(cam_in[:, C:], x, S, rowmap=cam_rows)
         self.state = st
@@ -362,7 +361,7 @@ class TrainGraph:
                 if last:
                     engine.run_block_train(pb, xm, 0, M, self._tape(("cam", bi), M, Cc, hid, F32, 0, False), fwd, None)
                 else:
-                    sc = runtime.scratch(self._sc.ws, M, Cc, hid, F32, self.dev, tag="_camfwd")
+                    sc = runtime.scratch(self._sc, M, Cc, hid, F32, self.dev, tag="_camfwd")
                     runtime.run_block(pb, xm, 0, M, sc, lambda qkv, o, fwd=fwd: fwd(qkv, o, None), None)
             if last:
                 ops.copy_rows(xm_out, xm, M)
@@ -497,9 +496,8 @@ class TrainGraph:
                 # the two blocks' dgrad GEMMs stage by stage as grouped launches (engine.block_bwd_multi)
                 engine.block_bwd_multi([rel, glo], tag="pair")
             else:
-                for it in (rel, glo):
-                    engine.block_bwd(it["pb"], it["bp"], it["g"], it["tape"], it["dx"], it["dxb"], it["attend_bwd"],
-                                     it["qkv_epi"], self._sc, tag=it["tag"])
+                for it in (rel, glo):  # one after another: both on the first scratch
+                    engine.block_bwd_multi([dict(it, sc=self._sc)])
             # anchor subsample: k-norm + RoPE backward -> K|V dgrad / wgrad -> LN1 (row map) backward
             epi = runtime.qkv_params(pr, rope, pos_rowmap=rowmap[l], **posctx)
             if epi is not None:

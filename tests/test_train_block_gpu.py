@@ -265,3 +265,88 @@ def test_block_backward_c4_global():
     assert rel(dx[others.to(DEV)], xr.grad[others]) < 3e-2, "input grad through dK / dV"
     for n, p in blk.named_parameters():
         assert rel(p.grad, ref[n].grad) < 3e-2, n
+
+
+@pytest.mark.parametrize("style", ["aggregator", "dino"])
+def test_block_pair_backward_bf16(style):
+    """The paired path (run_block_train_multi / block_bwd_multi: the layer's reloc and global
+    blocks stage by stage, their GEMM stages as grouped launches) at block level: two bf16 blocks
+    of different weights on disjoint row ranges of one x — global-like rows [0, 50) as 2 frames,
+    reloc-like rows [50, 125) as 3 — each against autograd through the oracle block exactly as
+    test_block_backward_bf16 (1e-2 forward, 3e-2 grads); a weight or tape swapped between the two
+    items is an order-1 error here.  The timer's launch counts show that the stages really were
+    shared: one launch per dgrad stage, one per weight where ops.wgrad_pair_splits pairs."""
+    from oracle import sfm_oracle as O
+    from sailrecon_amd import ops, runtime
+    from sailrecon_amd.layers.block import Block
+    from sailrecon_amd.layers.rope import RotaryPositionEmbedding2D
+    from sailrecon_amd.train import engine
+    from sailrecon_amd.train.params import FlatParams
+    torch.manual_seed(0)
+    C, H, gh, gw = 256, 4, 4, 5
+    P = 5 + gh * gw
+    agg = style == "aggregator"
+    dt = torch.bfloat16
+    spans = [("global", 0, 2), ("reloc", 2 * P, 3)]   # tag, first row, frames
+    R = 5 * P
+    x = torch.randn(R, C)
+    dy = torch.randn(R, C)
+    xd = x.to(DEV)
+    dx = dy.to(DEV)
+    dxb = dx.bfloat16()
+    fwd_items, bwd_items, keep = [], [], []
+    for seed, (tag, r0, frames) in enumerate(spans, 1):
+        r1 = r0 + frames * P
+        rope = RotaryPositionEmbedding2D(100) if agg else None
+        blk = Block(dim=C, num_heads=H, init_values=0.01, qk_norm=agg, rope=rope)
+        _randomize(blk, seed)
+        sd = {k: v.detach().clone() for k, v in blk.state_dict().items()}
+        blk = blk.to(DEV)
+        fp = FlatParams(blk)
+        blk.invalidate_packed()
+        pb = blk.packed(dt)
+        qkv_epi = None
+        if agg:
+            tabs = rope.tables(C // H, max(gh, gw) + 1, DEV)
+            qkv_epi = runtime.qkv_params(pb, tabs, pos_row_base=r0, tokens_per_frame=P, patch_start=5, grid_w=gw)
+        tape = engine.alloc_tape(r1 - r0, C, 4 * C, dt, DEV, frames * H * P, separate_raw=qkv_epi is not None)
+        fwd, bwd = engine.frame_attend_train(pb, frames, P)
+        fp.zero_grad()
+        fwd_items.append(dict(pb=pb, x=xd, r0=r0, r1=r1, tape=tape, attend=fwd, qkv_epi=qkv_epi))
+        bwd_items.append(dict(pb=pb, bp=engine.pack_bwd(blk, pb, dt), g=engine.block_grads(blk), tape=tape,
+                              dx=dx[r0:r1], dxb=dxb[r0:r1], attend_bwd=bwd, qkv_epi=qkv_epi, sc=engine.BwdScratch(),
+                              tag=tag))
+        keep.append((blk, sd, fp, r0, r1, frames))
+
+    # what the two items can share at these shapes, as ops itself decides it
+    a, b = bwd_items
+    dgrad_stages = [[dict(a=it["dxb"], w=getattr(it["bp"], w)) for it in bwd_items]
+                    for w in ("wt_fc2", "wt_fc1", "wt_proj", "wt_qkv")]
+    want_dgrad = sum(1 if ops.gemm_group_eligible(p) else len(p) for p in dgrad_stages)
+    rows = a["dx"].shape[0], b["dx"].shape[0]
+    paired = [engine._PAIR_WGRAD and ops.wgrad_pair_splits(*rows, *dw.shape) is not None
+              for dw in (a["g"].w_fc2, a["g"].w_fc1, a["g"].w_proj, a["g"].w_qkv)]
+    ops.TIMER = timer = ops.KernelTimer()
+    try:
+        engine.run_block_train_multi(fwd_items)
+        engine.block_bwd_multi(bwd_items, tag="pair")
+        torch.cuda.synchronize()
+    finally:
+        ops.TIMER = None
+    launches = {t: len(r) for t, r in timer.records.items()}
+    assert want_dgrad == 4 and launches.get("pair.dgrad", 0) == want_dgrad
+    assert launches.get("pair.wgrad", 0) == sum(paired)
+    assert not paired[3]  # qkv's 3 tiles of 256^2 do not fill a round evenly
+    for it in bwd_items:
+        assert launches.get(it["tag"] + ".wgrad", 0) == 4 - sum(paired)
+
+    for blk, sd, fp, r0, r1, frames in keep:  # reference: autograd through the oracle block, fp32 CPU
+        ref = {k: v.clone().requires_grad_(True) for k, v in sd.items() if v.is_floating_point()}
+        xr = x[r0:r1].clone().requires_grad_(True)
+        pos = _positions(frames, P, gw).view(frames, P, 2) if agg else None
+        y = O.block(ref, "", xr.view(frames, P, C), H, 1e-5, pos=pos, qk_norm=agg, rope_base=100.0 if agg else None)
+        y.backward(dy[r0:r1].view(frames, P, C))
+        assert rel(xd[r0:r1], y.detach().reshape(r1 - r0, C)) < 1e-2, (r0, "forward output")
+        assert rel(dx[r0:r1], xr.grad) < 3e-2, (r0, "input grad")
+        for n, p in blk.named_parameters():
+            assert rel(p.grad, ref[n].grad) < 3e-2, (r0, n)
