@@ -378,6 +378,28 @@ int sr_attn_merge_n(sr_stream_t stream, int dtype, int parts, int rows, int head
                     int64_t ld, int64_t part_rows, const float* lse_parts, const int* lse_seg_rows, void* out,
                     int64_t ldo, float* lse_out);
 
+/* Few query rows against long key segments, key-split (ABI 1.7): the camera-token rows of a
+ * pose-only forward's last global / global_reloc blocks (aggregator.py:414-423 reads only row 0 of
+ * every frame there), where sr_attention would launch one workgroup per head.  d as sr_attention's
+ * bf16 path with these restrictions (SR_EUNSUPPORTED otherwise): dtype SR_BF16, head_dim 64,
+ * lq <= 64, SR_MASK_NONE, no merge_o.  One or two key segments of any length (ragged included),
+ * batch >= 1 with the usual q_bstride / k0_bstride / k1_bstride (0 = shared), q_scaled honoured,
+ * any ldq (rows read in place from a packed q|k|v buffer), K / V as column slices.  No row past
+ * l0 / l1 of a segment is read, whatever tail_rows_readable says; key_bound / key_norm_max / boxes
+ * are ignored (plain online max).  o: bf16, row item * (o_bstride ? o_bstride : lq) + i (compact by
+ * default -- NOT q_bstride), ldo a multiple of 4; lse optional, [batch][heads][lq], log2 domain.
+ * The grid covers (key chunk, group of 4 heads, item): the logical key range [0, l0 + l1) is cut
+ * into sr_attention_rows_chunks(d) chunks of equal length (a multiple of 32; the last ones may be
+ * short or empty), chosen from the shape alone so that the launch reaches two workgroups per CU
+ * where chunks of >= 256 keys allow.  Each chunk's fp32 partial (unnormalised accumulator, running
+ * max, running sum) goes to `workspace` (16-B aligned, >= sr_attention_rows_workspace(d) bytes;
+ * stream-ordered reuse) and a second kernel folds them.  q / k / v 16-B aligned, o 8-B. */
+int sr_attention_rows(sr_stream_t stream, int dtype, const sr_attn_desc* d, void* workspace, int64_t workspace_bytes);
+/* bytes of workspace sr_attention_rows needs for d (0 for a description it rejects) */
+int64_t sr_attention_rows_workspace(const sr_attn_desc* d);
+/* key chunks sr_attention_rows cuts d's keys into (0 for a description it rejects) */
+int sr_attention_rows_chunks(const sr_attn_desc* d);
+
 /* fp8 (OCP e4m3) quantisation with ONE power-of-two scale per tensor (BASELINE C5, "fp8 QKV";
  * e4m3 Q/K/V with per-tensor scales):
  *   e = ceil(log2(amax(|mul * src|) / 448))   (0 for an all-zero tensor)

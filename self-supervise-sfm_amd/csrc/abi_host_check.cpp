@@ -277,6 +277,51 @@ void check() {
   b = attn(1, 8, 43968, 9728, 0);
   b.key_norm_max = 40.f;
   expect("sr_attention_pair head counts", sr_attention_pair(nullptr, SR_BF16, &a, &b), false);
+  // ---- few query rows, key-split (ABI 1.7): rejections, then the chunk plan of the C3 camera-row
+  // shapes and of ragged / two-segment / many-item ones (the launch itself fails without a device)
+  expect("sr_attention_rows null desc", sr_attention_rows(nullptr, SR_BF16, nullptr, fake(20), 1 << 30), false);
+  d = attn(1, 16, 65, 43968, 0);
+  expect("sr_attention_rows 65 rows", sr_attention_rows(nullptr, SR_BF16, &d, fake(20), 1 << 30), false);
+  if (sr_attention_rows_chunks(&d) != 0 || sr_attention_rows_workspace(&d) != 0) ++g_fail;
+  d = attn(1, 16, 32, 43968, 0);
+  d.head_dim = 128;
+  expect("sr_attention_rows head_dim 128", sr_attention_rows(nullptr, SR_BF16, &d, fake(20), 1 << 30), false);
+  d.head_dim = 64;
+  expect("sr_attention_rows f32", sr_attention_rows(nullptr, SR_F32, &d, fake(20), 1 << 30), false);
+  d.mask_mode = SR_MASK_CAMERA;
+  expect("sr_attention_rows mask", sr_attention_rows(nullptr, SR_BF16, &d, fake(20), 1 << 30), false);
+  d.mask_mode = SR_MASK_NONE;
+  d.merge_o = fake(8);
+  expect("sr_attention_rows merge_o", sr_attention_rows(nullptr, SR_BF16, &d, fake(20), 1 << 30), false);
+  d.merge_o = nullptr;
+  d.ldq = 3076;
+  expect("sr_attention_rows ldq % 8", sr_attention_rows(nullptr, SR_BF16, &d, fake(20), 1 << 30), false);
+  d.ldq = 1374 * 3072;  // camera rows read in place: one row per frame of a packed q|k|v buffer
+  d.k1 = (const char*)fake(5) + 2;  // a stale, unaligned segment-1 pointer is ignored while l1 == 0 ...
+  expect("sr_attention_rows stale k1 with l1 = 0", sr_attention_rows(nullptr, SR_BF16, &d, fake(20), 1 << 30), true);
+  d.v1 = fake(6);
+  d.ldk1 = d.ldv1 = d.ldk0;
+  d.l1 = 64;                        // ... and rejected once the segment is used
+  expect("sr_attention_rows unaligned k1", sr_attention_rows(nullptr, SR_BF16, &d, fake(20), 1 << 30), false);
+  d.l1 = 0;
+  d.k1 = d.v1 = nullptr;
+  expect("sr_attention_rows workspace too small",
+         sr_attention_rows(nullptr, SR_BF16, &d, fake(20), sr_attention_rows_workspace(&d) - 1), false);
+  expect("sr_attention_rows null workspace", sr_attention_rows(nullptr, SR_BF16, &d, nullptr, 1 << 30), false);
+  {
+    struct { int batch, heads, lq, l0, l1, chunks; } cases[] = {
+        {1, 16, 32, 43968, 0, 128}, {1, 16, 32, 9760, 0, 38}, {32, 16, 1, 1374, 0, 4}, {1, 16, 64, 4100, 0, 16},
+        {3, 6, 33, 1000, 64, 4},    {1, 1, 1, 1, 0, 1},       {3, 1, 2, 63, 21, 1},    {64, 16, 1, 1 << 20, 1 << 20, 2}};
+    for (const auto& c : cases) {
+      d = attn(c.batch, c.heads, c.lq, c.l0, c.l1);
+      const int n = sr_attention_rows_chunks(&d);
+      const int64_t ws = sr_attention_rows_workspace(&d);
+      std::printf("sr_attention_rows plan batch %d heads %d lq %d keys %d + %d: %d chunks, %lld workspace bytes\n", c.batch,
+                  c.heads, c.lq, c.l0, c.l1, n, (long long)ws);
+      if (n != c.chunks || ws != (int64_t)c.batch * c.heads * n * c.lq * 66 * 4) ++g_fail;
+      expect("sr_attention_rows launch", sr_attention_rows(nullptr, SR_BF16, &d, fake(20), ws), true);
+    }
+  }
   d = attn(1, 16, 43968, 43968, 0);
   std::printf("bound floats: %d\n", sr_attention_bound_floats(&d));
   std::printf("key box scratch floats: %d\n", sr_attention_key_box_scratch(43968, 1, 16));

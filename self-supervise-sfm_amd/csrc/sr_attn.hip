@@ -1706,6 +1706,270 @@ __global__ __launch_bounds__(256) void attn_merge_n_bf16_kernel(const bf16* __re
   }
 }
 
+// ------------------------------------------------------------------ few query rows, key-split
+// sr_attention_rows: at most 64 query rows per (item, head) against long key segments -- the camera
+// rows of a pose-only forward's last global / reloc blocks.  The work is the K/V stream, so the grid
+// splits the KEYS: workgroup (chunk, head group, item), its four waves on four adjacent heads of the
+// same key rows (512 contiguous bytes of every K / V row per workgroup), each wave alone with its
+// head -- no workgroup barrier.  Keys are one logical range [0, l0 + l1) cut into chunks of
+// chunk_keys (a multiple of the 32-key tile); a tile may straddle the segments (each lane resolves
+// its own key row) and a chunk past the last key is empty (its partial says max = -inf, sum = 0).
+// Per 32-key tile: S^T = K Q^T (lane = query, registers = keys), plain online max, P = exp2(S - m)
+// rounded to bf16, O^T += V^T P^T with the V tile staged row-major in the wave's own LDS slice and
+// read back transposed.  Partials (fp32 unnormalised O, running max, running sum) go to the
+// workspace; attn_rows_reduce_kernel folds the chunks and writes bf16 o and the LSE.
+struct RowsPlan {
+  int nchunk, chunk_keys, hgroups;
+};
+struct RowsArgs {
+  sr_attn_desc d;
+  int nchunk, chunk_keys;
+  float* ws_o;   // [item][head][chunk][lq][64]
+  float* ws_ml;  // [item][head][chunk][lq][2]  (max, sum)
+};
+constexpr int ROWS_KT = 32;         // keys per tile
+#ifndef SR_ROWS_HEADS_PER_WG
+#define SR_ROWS_HEADS_PER_WG 4      // 1: the (chunk, head) grid, one wave per workgroup (A/B builds only:
+                                    // the chunk plans that abi_host_check.cpp and tests/test_camera_only.py
+                                    // pin are those of the default, 4)
+#endif
+constexpr int ROWS_HW = SR_ROWS_HEADS_PER_WG;  // heads (= waves) per workgroup
+constexpr int ROWS_VLD = 72;        // 2-byte elements per staged V row (144 B: 16-B aligned, conflict-free)
+constexpr int ROWS_MIN_CHUNK = 256; // shortest planned chunk
+constexpr int ROWS_TARGET_WGS = 512 * 4 / ROWS_HW;  // two 4-wave workgroups per CU of a 256-CU chip
+
+// Pure host planning (no device query, so that it is the same everywhere and testable without one).
+inline RowsPlan rows_plan(const sr_attn_desc& d) {
+  RowsPlan p;
+  p.hgroups = (d.heads + ROWS_HW - 1) / ROWS_HW;
+  const int64_t total = (int64_t)d.l0 + d.l1;
+  const int64_t groups = (int64_t)p.hgroups * d.batch;
+  const int64_t want = (ROWS_TARGET_WGS + groups - 1) / groups;
+  const int64_t by_keys = std::max<int64_t>(1, total / ROWS_MIN_CHUNK);
+  p.nchunk = (int)std::max<int64_t>(1, std::min(want, by_keys));
+  const int64_t per = (total + p.nchunk - 1) / p.nchunk;
+  p.chunk_keys = (int)((per + ROWS_KT - 1) / ROWS_KT * ROWS_KT);
+  return p;
+}
+
+typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+
+template <int QB>
+__global__ __launch_bounds__(64 * ROWS_HW) void attn_rows_kernel(RowsArgs a) {
+  __shared__ __attribute__((aligned(16))) unsigned short vs_all[ROWS_HW][ROWS_KT * ROWS_VLD];
+  const sr_attn_desc& d = a.d;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int l32 = lane & 31, hi = lane >> 5;
+  const int chunk = blockIdx.x, head = blockIdx.y * ROWS_HW + wave, item = blockIdx.z;
+  if (head >= d.heads) return;  // wave-uniform; the kernel has no workgroup barrier
+  const int total = d.l0 + d.l1;
+  const int64_t kb64 = (int64_t)chunk * a.chunk_keys;
+  const int kbeg = (int)(kb64 < total ? kb64 : total);
+  const int kend = (int)(kb64 + a.chunk_keys < total ? kb64 + a.chunk_keys : total);
+  const int64_t part = ((int64_t)item * d.heads + head) * a.nchunk + chunk;
+  float* wo = a.ws_o + part * d.lq * 64;
+  float* wml = a.ws_ml + part * d.lq * 2;
+  if (kbeg >= kend) {  // empty chunk
+    if (hi == 0) {
+#pragma unroll
+      for (int b = 0; b < QB; ++b) {
+        const int qi = l32 + 32 * b;
+        if (qi < d.lq) {
+          wml[2 * qi] = -INFINITY;
+          wml[2 * qi + 1] = 0.f;
+        }
+      }
+    }
+    return;
+  }
+  unsigned short* vs = vs_all[wave];
+  const bf16x8 zero8 = {(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
+
+  // ---- Q fragments (B operand of S^T = K Q^T): lane (query l32, half hi) holds dims 32 hi + 8 s + j
+  // at step s -- the K fragment uses the same order, so each lane reads 64 contiguous bytes of a row
+  bf16x8 qf[QB][4];
+#pragma unroll
+  for (int b = 0; b < QB; ++b) {
+    const int qi = l32 + 32 * b;
+    if (qi < d.lq) {
+      const bf16* qp = (const bf16*)d.q + ((int64_t)item * d.q_bstride + qi) * d.ldq + head * 64 + 32 * hi;
+#pragma unroll
+      for (int s = 0; s < 4; ++s) qf[b][s] = *(const bf16x8*)(qp + 8 * s);
+    } else {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) qf[b][s] = zero8;
+    }
+  }
+  const float c = d.q_scaled ? 1.f : d.scale * 1.4426950408889634f;
+  const int colo = head * 64 + 32 * hi;
+  const bf16* const k0b = (const bf16*)d.k0 + (int64_t)item * d.k0_bstride * d.ldk0 + colo;
+  const bf16* const v0b = (const bf16*)d.v0 + (int64_t)item * d.k0_bstride * d.ldv0 + colo;
+  const bf16* const k1b = d.l1 > 0 ? (const bf16*)d.k1 + (int64_t)item * d.k1_bstride * d.ldk1 + colo : nullptr;
+  const bf16* const v1b = d.l1 > 0 ? (const bf16*)d.v1 + (int64_t)item * d.k1_bstride * d.ldv1 + colo : nullptr;
+  // lane (key l32, half hi): its key's 64 bytes of K and of V; zeros for a key past the last one
+  // (no row past a segment's end is ever read)
+  auto load = [&](int g0, bf16x8(&kf)[4], bf16x8(&vf)[4]) __attribute__((always_inline)) {
+    const int g = g0 + l32;
+    const bf16* kp = nullptr;
+    const bf16* vp = nullptr;
+    if (g < d.l0) {
+      kp = k0b + (int64_t)g * d.ldk0;
+      vp = v0b + (int64_t)g * d.ldv0;
+    } else if (g < total) {
+      kp = k1b + (int64_t)(g - d.l0) * d.ldk1;
+      vp = v1b + (int64_t)(g - d.l0) * d.ldv1;
+    }
+    if (kp) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        kf[s] = *(const bf16x8*)(kp + 8 * s);
+        vf[s] = *(const bf16x8*)(vp + 8 * s);
+      }
+    } else {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        kf[s] = zero8;
+        vf[s] = zero8;
+      }
+    }
+  };
+
+  float m_run[QB], l_run[QB];
+  f32x16 o[QB][2];
+#pragma unroll
+  for (int b = 0; b < QB; ++b) {
+    m_run[b] = -INFINITY;
+    l_run[b] = 0.f;
+#pragma unroll
+    for (int db = 0; db < 2; ++db)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) o[b][db][r] = 0.f;
+  }
+  bf16x8 kn[4], vn[4];
+  load(kbeg, kn, vn);
+  for (int g0 = kbeg; g0 < kend; g0 += ROWS_KT) {
+    bf16x8 kc[4];
+    // the wave's V tile, row-major [key][64 d] (LDS operations of one wave execute in order; the
+    // fences keep the compiler from moving the transposed reads across the writes)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      kc[s] = kn[s];
+      *(bf16x8*)(vs + l32 * ROWS_VLD + 32 * hi + 8 * s) = vn[s];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (g0 + ROWS_KT < kend) load(g0 + ROWS_KT, kn, vn);  // the next tile, under this one's arithmetic
+    // V^T fragments (A operand of O^T += V^T P^T): lane (d = 32 db + l32, half hi), element j of
+    // step t2 = key 16 t2 + 8 (j >> 2) + 4 hi + (j & 3), the key order of the P accumulator registers
+    bf16x8 vfr[2][2];
+#pragma unroll
+    for (int t2 = 0; t2 < 2; ++t2)
+#pragma unroll
+      for (int db = 0; db < 2; ++db) {
+        u16x8 u;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) u[j] = vs[(16 * t2 + 8 * (j >> 2) + 4 * hi + (j & 3)) * ROWS_VLD + 32 * db + l32];
+        vfr[t2][db] = __builtin_bit_cast(bf16x8, u);
+      }
+#pragma unroll
+    for (int b = 0; b < QB; ++b) {
+      f32x16 sc;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) sc[r] = 0.f;
+#pragma unroll
+      for (int s = 0; s < 4; ++s) sc = mfma32(kc[s], qf[b][s], sc);
+      float tmax = -INFINITY;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int key = g0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        sc[r] = key < total ? sc[r] * c : -INFINITY;
+        tmax = fmaxf(tmax, sc[r]);
+      }
+      tmax = max_x32(tmax);
+      const float m_new = fmaxf(m_run[b], tmax);  // finite: every tile of the loop holds a key
+      const float alpha = __builtin_amdgcn_exp2f(m_run[b] - m_new);
+      float psum = 0.f;
+      bf16x8 pf[2];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const bf16 pb = (bf16)__builtin_amdgcn_exp2f(sc[r] - m_new);
+        pf[r >> 3][r & 7] = pb;
+        psum += (float)pb;
+      }
+      l_run[b] = l_run[b] * alpha + psum;
+      m_run[b] = m_new;
+#pragma unroll
+      for (int db = 0; db < 2; ++db) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[b][db][r] *= alpha;
+#pragma unroll
+        for (int t2 = 0; t2 < 2; ++t2) o[b][db] = mfma32(vfr[t2][db], pf[t2], o[b][db]);
+      }
+    }
+  }
+  // ---- the chunk's partial: O^T register r of block db is d = 32 db + (r & 3) + 8 (r >> 2) + 4 hi
+#pragma unroll
+  for (int b = 0; b < QB; ++b) {
+    const float l = sum_x32(l_run[b]);
+    const int qi = l32 + 32 * b;
+    if (qi < d.lq) {
+#pragma unroll
+      for (int db = 0; db < 2; ++db)
+#pragma unroll
+        for (int rg = 0; rg < 4; ++rg) {
+          const f32x4 v = {o[b][db][4 * rg], o[b][db][4 * rg + 1], o[b][db][4 * rg + 2], o[b][db][4 * rg + 3]};
+          *(f32x4*)(wo + (int64_t)qi * 64 + 32 * db + 8 * rg + 4 * hi) = v;
+        }
+      if (hi == 0) {
+        wml[2 * qi] = m_run[b];
+        wml[2 * qi + 1] = l;
+      }
+    }
+  }
+}
+
+// One workgroup per (item, head, query row): thread (slice = tid / 16, d4 = tid % 16) folds chunks
+// slice, slice + 16, ... for columns 4 d4 .. 4 d4 + 3, then slice 0 folds the 16 slices.
+__global__ __launch_bounds__(256) void attn_rows_reduce_kernel(RowsArgs a) {
+  __shared__ float sm_m[16][16], sm_l[16][16];
+  __shared__ f32x4 sm_o[16][16];
+  const sr_attn_desc& d = a.d;
+  const int qi = blockIdx.x % d.lq, ih = blockIdx.x / d.lq;  // ih = item * heads + head
+  const int head = ih % d.heads, item = ih / d.heads;
+  const int d4 = threadIdx.x & 15, sl = threadIdx.x >> 4;
+  float m = -INFINITY, l = 0.f;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  auto fold = [&](float mc, float lc, const f32x4& oc) {
+    if (mc == -INFINITY) return;  // an empty chunk (or slice) contributes nothing
+    const float mn = fmaxf(m, mc);
+    const float wa = exp2f(m - mn), wb = exp2f(mc - mn);
+    l = l * wa + lc * wb;
+    acc = acc * wa + oc * wb;
+    m = mn;
+  };
+  for (int ch = sl; ch < a.nchunk; ch += 16) {
+    const int64_t part = (int64_t)ih * a.nchunk + ch;
+    const float mc = a.ws_ml[(part * d.lq + qi) * 2];
+    if (mc == -INFINITY) continue;  // its O rows were never written
+    fold(mc, a.ws_ml[(part * d.lq + qi) * 2 + 1], *(const f32x4*)(a.ws_o + (part * d.lq + qi) * 64 + 4 * d4));
+  }
+  sm_m[sl][d4] = m;
+  sm_l[sl][d4] = l;
+  sm_o[sl][d4] = acc;
+  __syncthreads();
+  if (sl != 0) return;
+  for (int s = 1; s < 16; ++s) fold(sm_m[s][d4], sm_l[s][d4], sm_o[s][d4]);
+  const float inv = l > 0.f ? 1.f / l : 0.f;
+  const int64_t orow = (int64_t)item * (d.o_bstride ? d.o_bstride : d.lq) + qi;
+  bf16x4 ob;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) ob[j] = (bf16)(acc[j] * inv);
+  *(bf16x4*)((bf16*)d.o + orow * d.ldo + head * 64 + 4 * d4) = ob;
+  if (d.lse && d4 == 0) d.lse[(int64_t)ih * d.lq + qi] = m == -INFINITY ? m : m + log2f(l);
+}
+
 }  // namespace
 
 extern "C" int sr_attention_key_box_scratch(int rows, int n_inst, int heads) {
@@ -1975,6 +2239,79 @@ extern "C" int sr_attn_merge(sr_stream_t stream, int dtype, int rows, int heads,
                        (const float*)o_b, ldb, lse_b, (float*)out, ldo, lse_out, rows, heads, head_dim);
   }
   return sr::check_launch("sr_attn_merge");
+}
+
+// Validation shared by sr_attention_rows and its two planning queries; `who` = NULL: quiet (the
+// queries return 0 for a description the entry would reject).
+static int rows_check(int dtype, const sr_attn_desc* desc, const char* who) {
+#define ROWS_CHECK(cond, code, ...)        \
+  do {                                     \
+    if (!(cond)) {                         \
+      if (who) sr::set_error(__VA_ARGS__); \
+      return (code);                       \
+    }                                      \
+  } while (0)
+  ROWS_CHECK(desc, SR_EINVAL, "%s: null desc", who);
+  const sr_attn_desc& d = *desc;
+  ROWS_CHECK(d.q && d.o && d.k0 && d.v0, SR_EINVAL, "%s: null q/k0/v0/o", who);
+  ROWS_CHECK(d.batch > 0 && d.batch <= 65535 && d.heads > 0 && d.heads <= 65535 && d.lq > 0 && d.l0 > 0 && d.l1 >= 0 &&
+                 (int64_t)d.l0 + d.l1 < (1LL << 31) - 64 && (int64_t)d.batch * d.heads * d.lq < (1LL << 31),
+             SR_EINVAL, "%s: bad sizes batch=%d heads=%d lq=%d l0=%d l1=%d", who, d.batch, d.heads, d.lq, d.l0, d.l1);
+  ROWS_CHECK(d.l1 == 0 || (d.k1 && d.v1), SR_EINVAL, "%s: segment 1 needs k1/v1", who);
+  ROWS_CHECK(dtype == SR_BF16, SR_EUNSUPPORTED, "%s: bf16 only (the f32 path runs sr_attention)", who);
+  ROWS_CHECK(d.head_dim == 64, SR_EUNSUPPORTED, "%s: head_dim must be 64 (got %d)", who, d.head_dim);
+  ROWS_CHECK(d.lq <= 64, SR_EUNSUPPORTED, "%s: at most 64 query rows per item (got %d)", who, d.lq);
+  ROWS_CHECK(d.mask_mode == SR_MASK_NONE && !d.mask, SR_EUNSUPPORTED, "%s: no masks", who);
+  ROWS_CHECK(!d.merge_o && !d.merge_lse, SR_EUNSUPPORTED, "%s: no merge_o (merge the results by their LSEs)", who);
+  ROWS_CHECK(d.q_scaled == 0 || d.q_scaled == 1, SR_EINVAL, "%s: q_scaled must be 0 or 1", who);
+  ROWS_CHECK(d.q_bstride >= 0 && d.k0_bstride >= 0 && d.k1_bstride >= 0 && d.o_bstride >= 0, SR_EINVAL,
+             "%s: negative item stride", who);
+  ROWS_CHECK(d.ldq % 8 == 0 && d.ldk0 % 8 == 0 && d.ldv0 % 8 == 0 && d.ldo % 4 == 0 && d.ldq >= 64 * d.heads &&
+                 d.ldk0 >= 64 * d.heads && d.ldv0 >= 64 * d.heads && d.ldo >= 64 * d.heads &&
+                 (d.l1 == 0 || (d.ldk1 % 8 == 0 && d.ldv1 % 8 == 0 && d.ldk1 >= 64 * d.heads && d.ldv1 >= 64 * d.heads)),
+             SR_EINVAL, "%s: leading dims must cover the heads and be multiples of 8 (ldo: of 4)", who);
+  ROWS_CHECK((((uintptr_t)d.q | (uintptr_t)d.k0 | (uintptr_t)d.v0) & 15) == 0 &&
+                 (d.l1 == 0 || (((uintptr_t)d.k1 | (uintptr_t)d.v1) & 15) == 0) && ((uintptr_t)d.o & 7) == 0 &&
+                 ((uintptr_t)d.lse & 3) == 0,
+             SR_EINVAL, "%s: q / k / v must be 16-B aligned, o 8-B, lse 4-B", who);
+#undef ROWS_CHECK
+  return SR_OK;
+}
+
+extern "C" int sr_attention_rows_chunks(const sr_attn_desc* desc) {
+  if (rows_check(SR_BF16, desc, nullptr) != SR_OK) return 0;
+  return rows_plan(*desc).nchunk;
+}
+
+extern "C" int64_t sr_attention_rows_workspace(const sr_attn_desc* desc) {
+  if (rows_check(SR_BF16, desc, nullptr) != SR_OK) return 0;
+  const RowsPlan p = rows_plan(*desc);
+  return (int64_t)desc->batch * desc->heads * p.nchunk * desc->lq * (64 + 2) * (int64_t)sizeof(float);
+}
+
+extern "C" int sr_attention_rows(sr_stream_t stream, int dtype, const sr_attn_desc* desc, void* workspace,
+                                 int64_t workspace_bytes) {
+  const int rc = rows_check(dtype, desc, "sr_attention_rows");
+  if (rc != SR_OK) return rc;
+  const sr_attn_desc& d = *desc;
+  const int64_t need = sr_attention_rows_workspace(desc);
+  SR_CHECK(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= need, SR_EINVAL,
+           "sr_attention_rows: the workspace must be 16-B aligned and hold sr_attention_rows_workspace(d) = %lld bytes "
+           "(got %lld)", (long long)need, (long long)workspace_bytes);
+  const RowsPlan p = rows_plan(d);
+  RowsArgs a;
+  a.d = d;
+  a.nchunk = p.nchunk;
+  a.chunk_keys = p.chunk_keys;
+  a.ws_o = (float*)workspace;
+  a.ws_ml = a.ws_o + (int64_t)d.batch * d.heads * p.nchunk * d.lq * 64;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(p.nchunk, p.hgroups, d.batch);
+  if (d.lq <= 32) hipLaunchKernelGGL(attn_rows_kernel<1>, grid, dim3(64 * ROWS_HW), 0, s, a);
+  else hipLaunchKernelGGL(attn_rows_kernel<2>, grid, dim3(64 * ROWS_HW), 0, s, a);
+  hipLaunchKernelGGL(attn_rows_reduce_kernel, dim3(d.batch * d.heads * d.lq), dim3(256), 0, s, a);
+  sr::note_kernel("attn_rows_kernel<%d>", d.lq <= 32 ? 1 : 2);
+  return sr::check_launch("sr_attention_rows");
 }
 
 extern "C" int sr_quant_fp8(sr_stream_t stream, const void* src, int64_t ld, int rows, int cols, float mul, void* dst,

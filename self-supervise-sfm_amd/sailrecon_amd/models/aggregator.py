@@ -275,7 +275,18 @@ class Aggregator(nn.Module):
 
 
     def forward(self, images: torch.Tensor, no_reloc_list: list, reloc_list: list,
-                fix_rank: Union[int, None] = None) -> Tuple[Dict[int, torch.Tensor], int, torch.Tensor]:
+                fix_rank: Union[int, None] = None, *, outputs: str = "all"
+                ) -> Tuple[Dict[int, torch.Tensor], int, torch.Tensor]:
+        """``outputs="camera"`` (single GPU, no kv_cache, at least one query frame; SR_CAMERA_ONLY=0
+        makes it behave as "all"): the caller reads only the camera-token row of every frame's last
+        layer (a pose-only SailRecon.forward: aggregator.py:414-423 and camera_head.py's
+        ``tokens[:, :, 0]``).  Then no intermediate map is allocated or copied, and the last layer's
+        global / global_reloc blocks project K / V for every row but run attention, proj, LN2 and the
+        MLP for the camera rows only (_layer_global_camera).  The returned dict is {depth - 1: t,
+        -1: t} with t [B, Nq, 1, 2C] -- the shape the frame-sharded path hands the camera head;
+        psi and the anchors' camera tokens are as with "all"."""
+        if outputs not in ("all", "camera"):
+            raise ValueError(f"outputs must be 'all' or 'camera', got {outputs!r}")
         B, S, C_in, H, W = images.shape
         num_recon, num_reloc = len(no_reloc_list), len(reloc_list)
         self.num_recon = num_recon
@@ -325,6 +336,7 @@ class Aggregator(nn.Module):
         imgs = imgs.reshape(F_, 3, H, W).float().contiguous()
 
         need_sub = Nq > 0 or fill_cache
+        camera = outputs == "camera" and _CAMERA_ONLY and G == 1 and not self.kv_cache and Nq > 0
         if fill_cache and B != 1:
             raise NotImplementedError("kv_cache needs B == 1 (aggregator.py:452)")
         host = {}
@@ -346,8 +358,10 @@ class Aggregator(nn.Module):
             self.last_subsample_indices = torch.from_numpy(idx)
             ftype = np.array(sum(([0 if a == 0 else 1 for a in my_anchors] + [2] * Nq_l for _ in range(B)), []),
                              dtype=np.int32)
-            anchors = np.array([b * S_l * P + a * P for b in range(B) for a in range(Na_l)], dtype=np.int32)
-            parts = [ftype, anchors]
+            anchors, queries = camera_row_tables(B, Na_l, Nq_l, P)
+            if not camera:
+                queries = queries[:0]
+            parts = [ftype, anchors, queries]
             if need_sub:
                 idx = idx[:, :, a_start:a_start + Na_l]                       # this rank's anchors
                 base = (np.arange(B) * S_l * P)[None, :, None, None] + (np.arange(Na_l) * P)[None, None, :, None]
@@ -356,12 +370,14 @@ class Aggregator(nn.Module):
                 parts.append(np.concatenate([spec, sel], axis=-1).astype(np.int32).reshape(-1))
             buf = runtime.to_device(torch.from_numpy(np.concatenate(parts)), dev)
             n0, n1 = len(ftype), len(ftype) + len(anchors)
-            host.update(Pp=Pp, anchor_rows0=buf[n0:n1],
-                        rowmap_t=buf[n1:].view(self.depth, B, Na_l * Pp) if need_sub else None)
+            n2 = n1 + len(queries)
+            host.update(Pp=Pp, anchor_rows0=buf[n0:n1], query_rows0=buf[n1:n2],
+                        rowmap_t=buf[n2:].view(self.depth, B, Na_l * Pp) if need_sub else None)
             return buf[:n0]
 
         x, sc = self._embed(imgs, F_, H, W, ftype_t_fn=host_tables, dtype=dtype)
         Pp, rowmap_t, anchor_rows0 = host["Pp"], host["rowmap_t"], host["anchor_rows0"]
+        query_rows0 = host["query_rows0"]
         if fill_cache:
             self._kv_cache_layers = [None] * self.depth
         rope = self.rope.tables(C // nh, max(gh, gw) + 1, dev) if self.rope is not None else None
@@ -369,9 +385,12 @@ class Aggregator(nn.Module):
 
         # ---- outputs (this rank's query frames)
         out_maps: Dict[int, torch.Tensor] = {}
-        if Nq > 0:
+        if Nq > 0 and not camera:
             for l in self.intermediate_layer_idx:
                 out_maps[l] = torch.empty(B, Nq_l, P, 2 * C, device=dev, dtype=torch.float32)
+        # camera mode: the queries' camera tokens only (frame half | reloc half), no maps
+        qcam = torch.empty(B, Nq_l, 1, 2 * C, device=dev, dtype=torch.float32) if camera else None
+        qcam_flat = qcam.view(B * Nq_l, 2 * C) if camera else None
         cam_loc = torch.empty(B, Na_l, 2 * C, device=dev, dtype=torch.float32)
         cam_flat = cam_loc.view(B * Na_l, 2 * C)
 
@@ -388,12 +407,24 @@ class Aggregator(nn.Module):
                                   x[b * S_l * P + Na_l * P:(b + 1) * S_l * P], Nq_l * P)
             if l == self.depth - 1:  # :414-423 frame half
                 ops.copy_rows(cam_flat[:, :C], x, B * Na_l, rowmap=anchor_rows0)
+                if camera:
+                    ops.copy_rows(qcam_flat[:, :C], x, B * Nq_l, rowmap=query_rows0)
             pr = self.global_reloc_blocks[l].packed(dtype)
             pg = self.global_blocks[l].packed(dtype)
             # the next reader of x after this layer's global / reloc blocks is the next frame block's LN1,
             # unless an output map or the camera tokens copy x first
             defer = l + 1 < self.depth and l not in out_maps and not fill_cache and \
                 os.environ.get("SR_CONCURRENT_STACKS", "0") != "1"
+            if camera and l == self.depth - 1:
+                # x is dead after this layer: only the camera rows' tails run, on a compact stream
+                for b in range(B):
+                    a0, q0, q1 = b * S_l * P, b * S_l * P + Na_l * P, (b + 1) * S_l * P
+                    self._layer_global_camera(pr, pg, x, sc, rowmap_t[l, b], Pp, a0, q0, q1, Na_l, Nq_l, P, rope,
+                                              posctx, dtype, dev, anchor_rows0[b * Na_l:(b + 1) * Na_l],
+                                              query_rows0[b * Nq_l:(b + 1) * Nq_l],
+                                              cam_flat[b * Na_l:(b + 1) * Na_l, C:],
+                                              qcam_flat[b * Nq_l:(b + 1) * Nq_l, C:])
+                break
             for b in range(B):
                 a0, q0, q1 = b * S_l * P, b * S_l * P + Na_l * P, (b + 1) * S_l * P
                 pending += self._layer_global(pr, pg, x, sc, rowmap_t[l, b] if need_sub else None, Pp, a0, q0, q1,
@@ -407,6 +438,8 @@ class Aggregator(nn.Module):
                 ops.copy_rows(cam_flat[:, C:], x, B * Na_l, rowmap=anchor_rows0)
 
         output_dict: Dict[int, torch.Tensor] = dict(out_maps)
+        if camera:
+            output_dict[self.depth - 1] = qcam
         assert (self.depth - 1 in output_dict) or Nq == 0, \
             f"Please make sure the last layer ({self.depth - 1}) is in the output_dict: {output_dict.keys()}"
         if Nq > 0:
@@ -699,9 +732,78 @@ class Aggregator(nn.Module):
             torch.cuda.current_stream(dev).wait_stream(side)  # join before the next frame block
         return out
 
+    def _layer_global_camera(self, pr, pg, x, sc, rowmap, Pp, a0, q0, q1, Na, Nq, P, rope, posctx, dtype, dev,
+                             anchor_rows, query_rows, cam_a, cam_q) -> None:
+        """The LAST layer's global_reloc + global blocks of one batch item when only the camera rows
+        are read (forward(outputs="camera"), G == 1): LN1 and the QKV projection run for every row as
+        in _layer_global (every row is a key), then only row 0 of each frame goes on --
+          * attention: the anchors' camera rows as one query set against every anchor token
+            (global); the queries' camera rows as one query set against the shared anchor subsample
+            and each against its own frame (batch = Nq, lq = 1), merged by their LSEs (reloc):
+            ops.attention_rows, sets of at most 64 rows;
+          * proj + LayerScale residual, LN2, fc1 + GELU, fc2 + LayerScale residual on a compact
+            [Na + Nq, C] fp32 stream gathered from x (runtime.run_block_tails: one grouped launch
+            per stage for the two blocks where eligible).
+        The results land in ``cam_a`` / ``cam_q`` ([Na, C] / [Nq, C] views); x is not updated.
+        fp32 compute runs the same plumbing on the exact sr_attention kernel."""
+        C, ws, H, D = pg.dim, self._ws, pg.heads, pg.head_dim
+        n_sub = Na * Pp
+        xn_sub = ws.get("xn_sub", n_sub, C, dtype, dev)
+        kv_sub = ws.get("kv_sub", n_sub, 2 * C, dtype, dev)
+        ops.layernorm(x, pr.ln1_w, pr.ln1_b, pr.eps, xn_sub, rowmap=rowmap, rows=n_sub)
+        epi_r = runtime.qkv_params(pr, rope, prescale=True, pos_row_base=q0, **posctx)
+        epi_g = runtime.qkv_params(pg, rope, prescale=True, pos_row_base=a0, **posctx)
+        epi_s = runtime.qkv_params(pr, rope, pos_rowmap=rowmap, **posctx)
+        if epi_s is not None:
+            epi_s["col_offset"] = C
+        probs = [dict(a=sc.xn[q0:q1], w=pr.w_qkv, out=sc.qkv[q0:q1], bias=pr.b_qkv, qkv=epi_r),
+                 dict(a=sc.xn[a0:q0], w=pg.w_qkv, out=sc.qkv[a0:q0], bias=pg.b_qkv, qkv=epi_g),
+                 dict(a=xn_sub, w=pr.w_qkv[C:], out=kv_sub, bias=_sl(pr.b_qkv, C, 3 * C), qkv=epi_s)]
+        if all(p_["qkv"] is not None for p_ in probs) and ops.gemm_group_eligible(probs):
+            ops.layernorm(x[q0:q1], pr.ln1_w, pr.ln1_b, pr.eps, sc.xn[q0:q1])
+            ops.layernorm(x[a0:q0], pg.ln1_w, pg.ln1_b, pg.eps, sc.xn[a0:q0])
+            ops.gemm_group(probs, _lib.SR_EPI_QKV, tag="gemm")
+        else:
+            runtime.run_block_head(pr, x, q0, q1, sc, epi_r, runtime.q_prescale(pr))
+            runtime.run_block_head(pg, x, a0, q0, sc, epi_g, runtime.q_prescale(pg))
+            self._kv_gemm(pr, xn_sub, kv_sub, rope, dict(pos_rowmap=rowmap, **posctx))
+        qkv_r, qkv_g = sc.qkv[q0:q1], sc.qkv[a0:q0]
+        n = Na + Nq
+        hid = pg.w_fc1.shape[0]
+        # compact scratch: rows [0, Na) the anchors' camera rows, [Na, n) the queries'
+        cs = runtime.BlockScratch(xn=ws.get("cam_xn", n, C, dtype, dev), qkv=ws.get("cam_y", n, C, dtype, dev),
+                                  o=ws.get("cam_o", n, C, dtype, dev), h=ws.get("cam_h", n, hid, dtype, dev))
+        xc = ws.get("cam_x", n, C, torch.float32, dev)
+        ops.copy_rows(xc[:Na], x, Na, rowmap=anchor_rows)
+        ops.copy_rows(xc[Na:], x, Nq, rowmap=query_rows)
+        # row 0 of every frame, read in place from the packed q|k|v rows (row stride P * 3C)
+        q_g = qkv_g.view(Na, P * 3 * C)[:, 0:C]
+        q_r = qkv_r.view(Nq, P * 3 * C)[:, 0:C]
+        for s0 in range(0, Na, ops.ROWS_MAX_LQ):
+            m = min(ops.ROWS_MAX_LQ, Na - s0)
+            ops.attention_rows(q_g[s0:s0 + m], qkv_g[:, C:2 * C], qkv_g[:, 2 * C:3 * C], cs.o[s0:s0 + m], heads=H,
+                               head_dim=D, batch=1, lq=m, q_bstride=0, l0=q0 - a0, k0_bstride=0, q_scaled=_qs(pg))
+        for s0 in range(0, Nq, ops.ROWS_MAX_LQ):
+            m = min(ops.ROWS_MAX_LQ, Nq - s0)
+            o_parts = ws.get("cam_parts", 2 * m, C, dtype, dev)
+            lse_parts = ws.get("cam_lse", 2, H * m, torch.float32, dev)
+            ops.attention_rows(q_r[s0:s0 + m], kv_sub[:, 0:C], kv_sub[:, C:2 * C], o_parts[:m], heads=H, head_dim=D,
+                               batch=1, lq=m, q_bstride=0, l0=n_sub, k0_bstride=0, lse=lse_parts[0],
+                               q_scaled=_qs(pr))
+            own = qkv_r[s0 * P:(s0 + m) * P]
+            ops.attention_rows(q_r[s0:s0 + m], own[:, C:2 * C], own[:, 2 * C:3 * C], o_parts[m:], heads=H, head_dim=D,
+                               batch=m, lq=1, q_bstride=1, l0=P, k0_bstride=P, lse=lse_parts[1], q_scaled=_qs(pr))
+            ops.attn_merge_n(o_parts, lse_parts, cs.o[Na + s0:Na + s0 + m], parts=2, rows=m, heads=H, head_dim=D,
+                             seg_rows=[m, 1])
+        runtime.run_block_tails([(pr, Na, n), (pg, 0, Na)], xc, cs, defer=False)
+        ops.copy_rows(cam_a, xc[:Na], Na)
+        ops.copy_rows(cam_q, xc[Na:], Nq)
+
     def set_fp8_global(self, enabled: bool = True, fp8_v: bool = False):
         """Global blocks' q.k^T in block-scaled fp8 (BASELINE C5); with ``fp8_v`` also V and P.V.
-        Everything else stays bf16."""
+        Everything else stays bf16 -- including the last layer of a camera-only forward
+        (forward(outputs="camera")), whose camera rows run the bf16 rows kernel: there is no fp8
+        rows kernel."""
         self.fp8_global = bool(enabled)
         self.fp8_v = bool(enabled and fp8_v)
         return self
@@ -848,6 +950,8 @@ _SHARD_TAIL = os.environ.get("SR_SHARD_TAIL", "0") == "1"
 # (profiles/r05_j10_rs_*.log): G = 8 69.03 / 69.15 -> 66.87 / 66.98 ms, G = 4 121.8 / 121.0 -> 120.9 /
 # 120.7 ms; the sharded GPU tests pass with it
 _SHARD_CONCURRENT = os.environ.get("SR_SHARD_CONCURRENT", "1") != "0"
+# SR_CAMERA_ONLY=0 (A/B switch): forward(outputs="camera") behaves as outputs="all"
+_CAMERA_ONLY = os.environ.get("SR_CAMERA_ONLY", "1") != "0"
 # smallest query set (in 256-row x head workgroups) whose reloc attention runs split (A/B switch)
 _RELOC_SPLIT_MIN_WG = int(os.environ.get("SR_RELOC_SPLIT_MIN_WG", "2048"))
 
@@ -872,6 +976,16 @@ def shard_range(n: int, G: int, r: int) -> Tuple[int, int]:
     ranks own one frame more than the rest (counts differ by at most one)."""
     base, extra = divmod(n, G)
     return r * base + min(r, extra), base + (1 if r < extra else 0)
+
+
+def camera_row_tables(B: int, Na: int, Nq: int, P: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Rows of the residual stream x that hold the camera token (row 0) of every anchor frame and of
+    every query frame, batch-major (int32): x orders each batch item's frames as [Na anchors ; Nq
+    queries] of P rows each, whatever the frames' original indices were."""
+    base = np.arange(B, dtype=np.int64)[:, None] * ((Na + Nq) * P)
+    anchors = (base + np.arange(Na, dtype=np.int64)[None, :] * P).reshape(-1)
+    queries = (base + (Na + np.arange(Nq, dtype=np.int64))[None, :] * P).reshape(-1)
+    return anchors.astype(np.int32), queries.astype(np.int32)
 
 
 def gather_rows(dst: torch.Tensor, src: torch.Tensor, counts: List[int], group, rank: int) -> list:

@@ -47,8 +47,11 @@ class SailRecon(nn.Module):
             no_reloc_list = list(range(rgbs.shape[1]))
         if reloc_list is None:
             reloc_list = list(range(rgbs.shape[1]))
+        # pose-only (both dense heads off): only the camera-token row of each frame's last layer is
+        # read below, so the aggregator may skip everything else of it (Aggregator.forward, outputs)
+        outputs = "camera" if self.point_head is None and self.depth_head is None else "all"
         rgb_feats, idx_patch, cam_token_last_layer = self.aggregator(rgbs, no_reloc_list, reloc_list,
-                                                                     fix_rank=fix_rank)
+                                                                     fix_rank=fix_rank, outputs=outputs)
         # frame-sharded aggregator (Aggregator.set_frame_sharding): this rank's query views only;
         # the camera head runs replicated on the gathered camera tokens of every view
         _, G, r = self.aggregator._world()

@@ -706,6 +706,62 @@ def attn_merge_n(o_parts: Tensor, lse_parts: Tensor, out: Tensor, *, parts: int,
     check(rc, "sr_attn_merge_n")
 
 
+ROWS_MAX_LQ = 64  # query rows per item of one sr_attention_rows launch
+
+
+def rows_chunks(*, heads: int, batch: int, lq: int, l0: int, l1: int = 0) -> int:
+    """Key chunks sr_attention_rows cuts a launch of this shape into (sr_attention_rows_chunks: the
+    library's own plan, a pure host function -- no device needed); 0 for a shape it rejects."""
+    d = AttnDesc()
+    fake = ctypes.c_void_p(1 << 12)  # the plan reads sizes only; pointers must just be non-null and aligned
+    d.q = d.k0 = d.v0 = d.o = fake
+    if l1 > 0:
+        d.k1 = d.v1 = fake
+        d.ldk1 = d.ldv1 = heads * 64
+    d.ldq = d.ldk0 = d.ldv0 = d.ldo = heads * 64
+    d.batch, d.heads, d.head_dim, d.lq, d.l0, d.l1 = batch, heads, 64, lq, l0, l1
+    return int(_lib.load().sr_attention_rows_chunks(ctypes.byref(d)))
+
+
+def attention_rows(q: Tensor, k0: Tensor, v0: Tensor, o: Tensor, *, heads: int, head_dim: int, batch: int, lq: int,
+                   q_bstride: int, l0: int, k0_bstride: int, k1: Optional[Tensor] = None, v1: Optional[Tensor] = None,
+                   l1: int = 0, k1_bstride: int = 0, scale: Optional[float] = None, lse: Optional[Tensor] = None,
+                   q_scaled: bool = False, tag: Optional[str] = "attn_rows") -> None:
+    """attention() for FEW query rows per item (lq <= 64) against long key segments: the bf16
+    key-split kernel (sr_attention_rows; the grid covers key chunks, fp32 partials in a per-stream
+    workspace, a second small kernel folds them).  Arguments as attention()'s, except that ``o`` is
+    compact: row item * lq + i ([batch * lq, >= heads * head_dim]), whatever q_bstride is -- q may be
+    rows picked in place from a packed q|k|v buffer through a large row stride.  ``lse`` fp32
+    [batch, heads, lq].  fp32 operands run the exact sr_attention kernel with the same description
+    (no fp32 rows kernel).  Timer class ``attn_rows`` (never attn_global: that one measures the pair
+    kernel); its byte model is the K + V stream, q and o, its flop model 4 lq keys head_dim."""
+    if lq > ROWS_MAX_LQ:
+        raise ValueError(f"attention_rows: at most {ROWS_MAX_LQ} query rows per item (chunk the set)")
+    if o.shape[0] < batch * lq:
+        raise ValueError("attention_rows: o must hold batch * lq compact rows")
+    d = _attn_desc(q, k0, v0, o, heads=heads, head_dim=head_dim, batch=batch, lq=lq, q_bstride=q_bstride, l0=l0,
+                   k0_bstride=k0_bstride, k1=k1, v1=v1, l1=l1, k1_bstride=k1_bstride, scale=scale, lse=lse,
+                   q_scaled=q_scaled)
+    d.o_bstride = lq
+    timed = TIMER is not None and TIMER.wants(tag)
+    ev0 = TIMER.start() if timed else None
+    lib = _lib.load()
+    if q.dtype == torch.bfloat16:
+        nbytes_ws = int(lib.sr_attention_rows_workspace(ctypes.byref(d)))
+        if nbytes_ws <= 0:
+            # the entry's own message (head_dim, alignment, ...)
+            check(lib.sr_attention_rows(_stream(q), dtype_code(q.dtype), ctypes.byref(d), None, 0), "sr_attention_rows")
+        ws = _train_ws(q.device, "attn_rows", (nbytes_ws + 3) // 4)
+        check(lib.sr_attention_rows(_stream(q), dtype_code(q.dtype), ctypes.byref(d), _p(ws), ws.numel() * 4),
+              "sr_attention_rows")
+    else:
+        check(lib.sr_attention(_stream(q), dtype_code(q.dtype), ctypes.byref(d)), "sr_attention")
+    if timed:
+        keys = (l0 if k0_bstride == 0 else batch * l0) + (l1 if k1_bstride == 0 else batch * l1)
+        TIMER.stop(tag, ev0, 4.0 * batch * heads * lq * (l0 + l1) * head_dim,
+                   q.element_size() * heads * head_dim * (2 * batch * lq + 2 * keys), kernel=last_kernel())
+
+
 def quant_fp8(src: Tensor, mul: float, dst: Optional[Tensor] = None, exp_out: Optional[Tensor] = None):
     """e4m3 copy of ``mul * src`` (bf16 [rows, cols]) with one power-of-two scale (sr_quant_fp8):
     returns (dst uint8 [rows, cols], exp int32 device scalar) with mul * src ~= dst * 2^exp."""

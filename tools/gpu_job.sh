@@ -180,6 +180,14 @@ for step in "$@"; do
     pmc_pair) run pmc_pair1 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT -d gpurun_out/pmc_pair1 -o run --output-format csv -- python3 tools/kbench.py attn_pair && \
               run pmc_pair2 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_INSTS_SALU GRBM_GUI_ACTIVE -d gpurun_out/pmc_pair2 -o run --output-format csv -- python3 tools/kbench.py attn_pair && \
               run pmc_pair3 300 rocprofv3 --pmc SQ_INSTS_VALU_TRANS_F32 SQ_ACTIVE_INST_MISC SQ_ACTIVE_INST_SCA SQ_INSTS_SMEM SQ_INST_CYCLES_VMEM_RD GRBM_GUI_ACTIVE -d gpurun_out/pmc_pair3 -o run --output-format csv -- python3 tools/kbench.py attn_pair ;;
+    krows)   run krows 300 python tools/kbench.py attn_rows ;;
+    rows_tests) run rows_tests 400 python -u -m pytest tests/test_attn_rows_gpu.py tests/test_camera_only_gpu.py -x -q -s -m gpu ;;
+    camera_parity) run camera_parity 300 python tools/camera_parity.py g10_518_n32 bf16 ;;
+    camera_ab) for i in 1 2 3; do  # the camera-only last layer off / on
+                 for sw in 0 1; do
+                   run bench_co${sw}_$i 240 env SR_CAMERA_ONLY=$sw python bench.py --gpus 1 --steps 20 --warmup 3 || exit 1
+                 done
+               done ;;
     *) echo "unknown step $step"; exit 2 ;;
   esac
 done

@@ -875,6 +875,51 @@ def train():
     print(f"train: box calibration {cal['tflops']} TF/s ({cal['kernel']}, {cal['shape']})", flush=True)
 
 
+def attn_rows():
+    """The camera rows of a pose-only C3 forward's last layer (ops.attention_rows, sr_attention_rows):
+    32 rows x 43,968 keys (global), and 32 rows x 9,760 subsample keys + 1,374 own-frame keys with
+    the LSE merge (reloc); 16 heads, the rows read in place from the packed q|k|v buffer.  Time and
+    achieved GB/s against the K + V bytes of each launch."""
+    C, H, D, P, N = 1024, 16, 64, 1374, 32
+    nsub = N * 305
+    qkv = torch.randn(N * P, 3 * C, device=DEV, dtype=torch.bfloat16)
+    kv = torch.randn(nsub, 2 * C, device=DEV, dtype=torch.bfloat16)
+    q = qkv.view(N, P * 3 * C)[:, :C]
+    o = torch.empty(N, C, device=DEV, dtype=torch.bfloat16)
+    o_parts = torch.empty(2 * N, C, device=DEV, dtype=torch.bfloat16)
+    lse_parts = torch.empty(2, H * N, device=DEV)
+    kw = dict(heads=H, head_dim=D, tag=None)
+
+    def glob():
+        ops.attention_rows(q, qkv[:, C:2 * C], qkv[:, 2 * C:], o, batch=1, lq=N, q_bstride=0, l0=N * P, k0_bstride=0, **kw)
+
+    def sub():
+        ops.attention_rows(q, kv[:, :C], kv[:, C:], o_parts[:N], batch=1, lq=N, q_bstride=0, l0=nsub, k0_bstride=0,
+                           lse=lse_parts[0], **kw)
+
+    def own():
+        ops.attention_rows(q, qkv[:, C:2 * C], qkv[:, 2 * C:], o_parts[N:], batch=N, lq=1, q_bstride=1, l0=P,
+                           k0_bstride=P, lse=lse_parts[1], **kw)
+
+    def merge():
+        ops.attn_merge_n(o_parts, lse_parts, o, parts=2, rows=N, heads=H, head_dim=D, seg_rows=[N, 1])
+
+    def reloc():
+        sub()
+        own()
+        merge()
+    for name, fn, keys in (("global 32 x 43968", glob, N * P), ("reloc subsample 32 x 9760", sub, nsub),
+                           ("reloc own 32 x (1 x 1374)", own, N * P), ("reloc merge", merge, 0),
+                           ("reloc 32 x (9760 + 1374)", reloc, nsub + N * P)):
+        ms = timeit(fn, reps=20, warm=3)
+        nb = 2.0 * keys * C * 2
+        if fn is merge:  # no K / V stream, and sr_attn_merge_n does not report its kernel
+            print(f"attn_rows {name:28s} {ms * 1e3:8.1f} us  (attn_merge_n_bf16_kernel)")
+            continue
+        print(f"attn_rows {name:28s} {ms * 1e3:8.1f} us  {nb / 1e6:7.1f} MB K+V  {nb / ms / 1e6:8.1f} GB/s  "
+              f"({ops.last_kernel()})")
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["attn", "gemm", "ln"]
     for w in which:
