@@ -717,6 +717,29 @@ int sr_residual_layernorm(sr_stream_t stream, int dtype, float* x, int64_t ldx, 
  * to kpad: out[(f*gh+py)*gw+px][c*ps*ps + ky*ps + kx]  (patch_embed.py:78) */
 int sr_im2col_normalize(sr_stream_t stream, int dtype, const float* img, int frames, int H, int W,
                         int patch, const float* mean3, const float* std3, void* out, int kpad);
+/* sr_im2col_normalize of selected frames (ABI 1.8): output frame u reads source frame
+ * frame_map[u] (device int32 [frames]; NULL: u), so the distinct frames of sr_frame_groups reach
+ * the patch GEMM without a gather pass.  `frames` counts output frames. */
+int sr_im2col_normalize_map(sr_stream_t stream, int dtype, const float* img, const int32_t* frame_map, int frames,
+                            int H, int W, int patch, const float* mean3, const float* std3, void* out, int kpad);
+
+/* ------------------------------------------------------------------------
+ * Bit-identical frames (ABI 1.8).  n_frames frames of frame_words 32-bit words each, frame f at
+ * frames + f * frame_stride_words words (4-byte alignment suffices; compared as bits, so +0 and
+ * -0 differ and equal NaN patterns are equal).  out[f] (device int32 [n_frames]) = the smallest
+ * g < f whose frame holds the same bits as frame f where the search finds one, else f; out[g] = g
+ * for every g that is named.  The search: a 128-bit fingerprint per frame (two wrapping sums over
+ * (word, index) hashes, so chunking and order do not matter) names for each f the first frame
+ * with an equal fingerprint, and a bitwise compare of that one pair decides -- a fingerprint
+ * collision can only lose a group, never make one.  fp_override (optional, device
+ * uint64 [n_frames][2]) replaces the computed fingerprints (tests force collisions with it).
+ * Four launches on `stream`, no host synchronisation; `workspace`: sr_frame_groups_workspace
+ * bytes (0: arguments out of range), 8-byte aligned.  1 <= n_frames <= 65535,
+ * 1 <= frame_words < 2^31.
+ * ---------------------------------------------------------------------- */
+int64_t sr_frame_groups_workspace(int64_t frame_words, int n_frames);
+int sr_frame_groups(sr_stream_t stream, const void* frames, int64_t frame_words, int64_t frame_stride_words,
+                    int n_frames, const uint64_t* fp_override, int32_t* out, void* workspace);
 
 /* x[f*tokens_per_frame + t] = table[type_of_frame[f]][t] for t < n_special
  * (aggregator.py:287-299, vision_transformer.py:250-257) */

@@ -453,6 +453,37 @@ void check() {
     expect("sr_weight_refresh_list_bf16 empty", sr_weight_refresh_list_bf16(nullptr, 0, nullptr, nullptr, 0), false);
   }
   expect("sr_im2col_normalize null", sr_im2col_normalize(nullptr, SR_BF16, nullptr, 0, 518, 518, 14, nullptr, nullptr, nullptr, 0), false);
+  {
+    // ---- sr_im2col_normalize_map / sr_frame_groups (ABI 1.8)
+    const float m3[3] = {0.f, 0.f, 0.f}, s3[3] = {1.f, 1.f, 1.f};
+    expect("sr_im2col_normalize_map null", sr_im2col_normalize_map(nullptr, SR_BF16, nullptr, fake<int32_t>(2), 2, 56, 56, 14, m3, s3, fake(3), 640), false);
+    expect("sr_im2col_normalize_map H % patch", sr_im2col_normalize_map(nullptr, SR_BF16, fake<float>(1), fake<int32_t>(2), 2, 57, 56, 14, m3, s3, fake(3), 640), false);
+    expect("sr_im2col_normalize_map kpad", sr_im2col_normalize_map(nullptr, SR_F32, fake<float>(1), fake<int32_t>(2), 2, 56, 56, 14, m3, s3, fake(3), 512), false);
+    expect("sr_im2col_normalize_map dtype", sr_im2col_normalize_map(nullptr, 7, fake<float>(1), fake<int32_t>(2), 2, 56, 56, 14, m3, s3, fake(3), 640), false);
+    expect("sr_im2col_normalize_map", sr_im2col_normalize_map(nullptr, SR_BF16, fake<float>(1), fake<int32_t>(2), 2, 56, 56, 14, m3, s3, fake(3), 640), true);
+    const int64_t fw = 3 * 518 * 518;
+    const int64_t need = sr_frame_groups_workspace(fw, 64);
+    // 50 chunks of 16,384 words: 64 * (50 * 16 + 16 + 8) bytes
+    const bool ws_ok = need == 64 * (50 * 16 + 24) && sr_frame_groups_workspace(1, 1) == 48 &&
+                       sr_frame_groups_workspace(0, 4) == 0 && sr_frame_groups_workspace(fw, 0) == 0 &&
+                       sr_frame_groups_workspace(fw, 65536) == 0 && sr_frame_groups_workspace(int64_t(1) << 31, 2) == 0;
+    std::printf("%-44s %sbytes %lld\n", "sr_frame_groups_workspace", ws_ok ? "" : "UNEXPECTED  ", (long long)need);
+    if (!ws_ok) ++g_fail;
+    int32_t* rep = fake<int32_t>(5);
+    expect("sr_frame_groups null frames", sr_frame_groups(nullptr, nullptr, fw, fw, 64, nullptr, rep, fake(6)), false);
+    expect("sr_frame_groups null out", sr_frame_groups(nullptr, fake(4), fw, fw, 64, nullptr, nullptr, fake(6)), false);
+    expect("sr_frame_groups null workspace", sr_frame_groups(nullptr, fake(4), fw, fw, 64, nullptr, rep, nullptr), false);
+    expect("sr_frame_groups no frames", sr_frame_groups(nullptr, fake(4), fw, fw, 0, nullptr, rep, fake(6)), false);
+    expect("sr_frame_groups too many frames", sr_frame_groups(nullptr, fake(4), fw, fw, 65536, nullptr, rep, fake(6)), false);
+    expect("sr_frame_groups no words", sr_frame_groups(nullptr, fake(4), 0, fw, 2, nullptr, rep, fake(6)), false);
+    expect("sr_frame_groups 2^31 words", sr_frame_groups(nullptr, fake(4), int64_t(1) << 31, int64_t(1) << 31, 2, nullptr, rep, fake(6)), false);
+    expect("sr_frame_groups stride < words", sr_frame_groups(nullptr, fake(4), fw, fw - 1, 2, nullptr, rep, fake(6)), false);
+    expect("sr_frame_groups frames % 4", sr_frame_groups(nullptr, (const char*)fake(4) + 2, fw, fw, 2, nullptr, rep, fake(6)), false);
+    expect("sr_frame_groups workspace % 8", sr_frame_groups(nullptr, fake(4), fw, fw, 2, nullptr, rep, (char*)fake(6) + 4), false);
+    expect("sr_frame_groups fp_override % 8", sr_frame_groups(nullptr, fake(4), fw, fw, 2, (const uint64_t*)((char*)fake(7) + 4), rep, fake(6)), false);
+    expect("sr_frame_groups", sr_frame_groups(nullptr, (const char*)fake(4) + 4, fw, fw + 1, 64, nullptr, rep, fake(6)), true);
+    expect("sr_frame_groups one frame, override", sr_frame_groups(nullptr, fake(4), 5, 0, 1, fake<uint64_t>(7), rep, fake(6)), true);
+  }
 }
 
 }  // namespace

@@ -289,9 +289,11 @@ int residual_layernorm_dispatch(hipStream_t s, float* x, int64_t ldx, const TY* 
 }
 
 // ------------------------------------------------------------------ im2col
+// frame_map (optional): output frame f reads source frame frame_map[f]
 template <typename T>
-__global__ void im2col_kernel(const float* __restrict__ img, int frames, int H, int W, int ps, float m0, float m1,
-                              float m2, float s0, float s1, float s2, T* __restrict__ out, int kpad) {
+__global__ void im2col_kernel(const float* __restrict__ img, const int32_t* __restrict__ frame_map, int frames, int H,
+                              int W, int ps, float m0, float m1, float m2, float s0, float s1, float s2,
+                              T* __restrict__ out, int kpad) {
   const int gh = H / ps, gw = W / ps, kk = 3 * ps * ps;
   const int64_t total = (int64_t)frames * gh * gw * kpad;
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
@@ -300,7 +302,8 @@ __global__ void im2col_kernel(const float* __restrict__ img, int frames, int H, 
     float v = 0.f;
     if (k < kk) {
       const int px = (int)(r % gw), py = (int)((r / gw) % gh);
-      const int64_t f = r / ((int64_t)gw * gh);
+      const int64_t fo = r / ((int64_t)gw * gh);
+      const int64_t f = frame_map ? (int64_t)frame_map[fo] : fo;
       const int c = k / (ps * ps), ky = (k / ps) % ps, kx = k % ps;
       const float raw = img[((f * 3 + c) * H + (py * ps + ky)) * (int64_t)W + px * ps + kx];
       const float mean = c == 0 ? m0 : (c == 1 ? m1 : m2);
@@ -310,6 +313,140 @@ __global__ void im2col_kernel(const float* __restrict__ img, int frames, int H, 
     out[e] = sr::from_f32<T>(v);
   }
 }
+
+// ------------------------------------------------------------------ bit-identical frame groups
+// sr_frame_groups: a 128-bit fingerprint per frame picks, for every frame, the earliest frame that
+// could be its copy; a bitwise compare of that one pair decides.  Frames are 32-bit words with
+// 4-byte alignment; a frame's words from its first 16-B boundary on are read as 16-B vectors, the
+// up to 3 words before it and after the last whole vector one by one.
+constexpr int FG_CHUNK_VEC = 4096;  // 16-B vectors per (chunk, frame) workgroup: 64 KiB, 16 loads per thread
+
+__device__ __forceinline__ uint32_t fg_fmix(uint32_t x) {  // MurmurHash3's 32-bit finaliser
+  x ^= x >> 16;
+  x *= 0x85EBCA6Bu;
+  x ^= x >> 13;
+  x *= 0xC2B2AE35u;
+  x ^= x >> 16;
+  return x;
+}
+// word w at index i -> two 64-bit terms; the sums wrap and commute, so neither the split into
+// chunks nor the order inside one changes the fingerprint
+__device__ __forceinline__ void fg_mix(uint32_t w, uint32_t i, uint64_t& s1, uint64_t& s2) {
+  const uint32_t p = fg_fmix(w ^ (i * 0x9E3779B1u + 0x7F4A7C15u));
+  const uint32_t q = fg_fmix((w + 0x165667B1u) ^ (i * 0x85EBCA77u + 0x27D4EB2Fu));
+  s1 += ((uint64_t)p << 32) | q;
+  s2 += (uint64_t)p * (uint64_t)(q | 1u);
+}
+__device__ __forceinline__ int64_t fg_min(int64_t a, int64_t b) { return a < b ? a : b; }
+// words before the frame's first 16-B boundary
+__device__ __forceinline__ int64_t fg_head(const uint32_t* base, int64_t fw) {
+  const int64_t h = (int64_t)(((16u - (uint32_t)((uintptr_t)base & 15u)) & 15u) >> 2);
+  return h < fw ? h : fw;
+}
+
+// grid (chunk, frame): partials[(f * chunks + c) * 2 + {0, 1}]
+__global__ __launch_bounds__(256) void frame_fingerprint_kernel(const uint32_t* __restrict__ frames, int64_t fw,
+                                                                int64_t stride, int chunks,
+                                                                uint64_t* __restrict__ partials) {
+  __shared__ uint64_t red[2][256];
+  const int tid = threadIdx.x, c = blockIdx.x, f = blockIdx.y;
+  const uint32_t* base = frames + (int64_t)f * stride;
+  const int64_t head = fg_head(base, fw);
+  const int64_t nvec = (fw - head) / 4, tail0 = head + nvec * 4;
+  uint64_t s1 = 0, s2 = 0;
+  const int64_t v1 = fg_min(nvec, ((int64_t)c + 1) * FG_CHUNK_VEC);
+  for (int64_t v = (int64_t)c * FG_CHUNK_VEC + tid; v < v1; v += 256) {
+    const int64_t i = head + 4 * v;
+    const uint4 t = *(const uint4*)(base + i);
+    fg_mix(t.x, (uint32_t)i, s1, s2);
+    fg_mix(t.y, (uint32_t)i + 1u, s1, s2);
+    fg_mix(t.z, (uint32_t)i + 2u, s1, s2);
+    fg_mix(t.w, (uint32_t)i + 3u, s1, s2);
+  }
+  if (c == 0) {  // head and tail words (at most 3 each)
+    if (tid < head) fg_mix(base[tid], (uint32_t)tid, s1, s2);
+    if (tid >= 64 && tail0 + (tid - 64) < fw) fg_mix(base[tail0 + (tid - 64)], (uint32_t)(tail0 + (tid - 64)), s1, s2);
+  }
+  red[0][tid] = s1;
+  red[1][tid] = s2;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) {
+      red[0][tid] += red[0][tid + s];
+      red[1][tid] += red[1][tid + s];
+    }
+    __syncthreads();
+  }
+  if (tid < 2) partials[((int64_t)f * chunks + c) * 2 + tid] = red[tid][0];
+}
+
+// one workgroup: fp[f] = sum of frame f's partials (or the caller's override), then cand[f] = the
+// smallest g <= f with fp[g] == fp[f]; equal[f] = 1 until a compare says otherwise
+__global__ __launch_bounds__(256) void frame_candidate_kernel(const uint64_t* __restrict__ partials, int chunks,
+                                                              const uint64_t* __restrict__ fp_override, int n,
+                                                              uint64_t* fp, int32_t* __restrict__ cand,
+                                                              int32_t* __restrict__ equal) {
+  for (int f = threadIdx.x; f < n; f += 256) {
+    uint64_t a = 0, b = 0;
+    if (fp_override) {
+      a = fp_override[2 * f];
+      b = fp_override[2 * f + 1];
+    } else {
+      for (int c = 0; c < chunks; ++c) {
+        a += partials[((int64_t)f * chunks + c) * 2];
+        b += partials[((int64_t)f * chunks + c) * 2 + 1];
+      }
+    }
+    fp[2 * f] = a;
+    fp[2 * f + 1] = b;
+  }
+  __syncthreads();
+  for (int f = threadIdx.x; f < n; f += 256) {
+    const uint64_t a = fp[2 * f], b = fp[2 * f + 1];
+    int g = 0;
+    while (g < f && !(fp[2 * g] == a && fp[2 * g + 1] == b)) ++g;
+    cand[f] = g;
+    equal[f] = 1;
+  }
+}
+
+// grid (chunk, frame): frame f against frame cand[f], word for word; every writer stores the same 0
+__global__ __launch_bounds__(256) void frame_compare_kernel(const uint32_t* __restrict__ frames, int64_t fw,
+                                                            int64_t stride, const int32_t* __restrict__ cand,
+                                                            int32_t* __restrict__ equal) {
+  const int tid = threadIdx.x, c = blockIdx.x, f = blockIdx.y;
+  const int g = cand[f];
+  if (g == f) return;
+  const uint32_t* a = frames + (int64_t)f * stride;
+  const uint32_t* b = frames + (int64_t)g * stride;
+  const int64_t head = fg_head(a, fw);
+  bool diff = false;
+  if (head == fg_head(b, fw)) {  // the two frames reach a 16-B boundary at the same word
+    const int64_t nvec = (fw - head) / 4, tail0 = head + nvec * 4;
+    const int64_t v1 = fg_min(nvec, ((int64_t)c + 1) * FG_CHUNK_VEC);
+    for (int64_t v = (int64_t)c * FG_CHUNK_VEC + tid; v < v1; v += 256) {
+      const uint4 s = *(const uint4*)(a + head + 4 * v);
+      const uint4 t = *(const uint4*)(b + head + 4 * v);
+      diff |= (s.x != t.x) | (s.y != t.y) | (s.z != t.z) | (s.w != t.w);
+    }
+    if (c == 0) {
+      if (tid < head) diff |= a[tid] != b[tid];
+      if (tid >= 64 && tail0 + (tid - 64) < fw) diff |= a[tail0 + (tid - 64)] != b[tail0 + (tid - 64)];
+    }
+  } else {
+    const int64_t w1 = fg_min(fw, ((int64_t)c + 1) * 4 * FG_CHUNK_VEC);
+    for (int64_t i = (int64_t)c * 4 * FG_CHUNK_VEC + tid; i < w1; i += 256) diff |= a[i] != b[i];
+  }
+  if (diff) equal[f] = 0;
+}
+
+__global__ void frame_rep_kernel(const int32_t* __restrict__ cand, const int32_t* __restrict__ equal, int n,
+                                 int32_t* __restrict__ out) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f < n) out[f] = equal[f] ? cand[f] : f;
+}
+
+inline int fg_chunks(int64_t fw) { return (int)(((fw + 3) / 4 + FG_CHUNK_VEC - 1) / FG_CHUNK_VEC); }
 
 // ------------------------------------------------------------------ token fills / copies
 __global__ void special_tokens_kernel(float* __restrict__ x, int64_t ldx, int frames, int tpf, int nspec,
@@ -489,19 +626,64 @@ extern "C" int sr_layernorm_copy(sr_stream_t stream, int out_dtype, const float*
 
 extern "C" int sr_im2col_normalize(sr_stream_t stream, int dtype, const float* img, int frames, int H, int W,
                                    int patch, const float* mean3, const float* std3, void* out, int kpad) {
+  return sr_im2col_normalize_map(stream, dtype, img, nullptr, frames, H, W, patch, mean3, std3, out, kpad);
+}
+
+extern "C" int sr_im2col_normalize_map(sr_stream_t stream, int dtype, const float* img, const int32_t* frame_map,
+                                       int frames, int H, int W, int patch, const float* mean3, const float* std3,
+                                       void* out, int kpad) {
   SR_CHECK(img && out && mean3 && std3, SR_EINVAL, "sr_im2col_normalize: null pointer");
+  SR_CHECK(dtype == SR_BF16 || dtype == SR_F32, SR_EINVAL, "sr_im2col_normalize: bad dtype %d", dtype);
   SR_CHECK(frames > 0 && patch > 0 && H % patch == 0 && W % patch == 0, SR_EINVAL,
            "sr_im2col_normalize: H=%d W=%d not multiples of patch %d", H, W, patch);
   SR_CHECK(kpad >= 3 * patch * patch, SR_EINVAL, "sr_im2col_normalize: kpad too small");
   const int64_t total = (int64_t)frames * (H / patch) * (W / patch) * kpad;
   hipStream_t s = (hipStream_t)stream;
   if (dtype == SR_BF16)
-    hipLaunchKernelGGL(im2col_kernel<bf16>, grid_for(total), dim3(256), 0, s, img, frames, H, W, patch, mean3[0],
-                       mean3[1], mean3[2], std3[0], std3[1], std3[2], (bf16*)out, kpad);
+    hipLaunchKernelGGL(im2col_kernel<bf16>, grid_for(total), dim3(256), 0, s, img, frame_map, frames, H, W, patch,
+                       mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], (bf16*)out, kpad);
   else
-    hipLaunchKernelGGL(im2col_kernel<float>, grid_for(total), dim3(256), 0, s, img, frames, H, W, patch, mean3[0],
-                       mean3[1], mean3[2], std3[0], std3[1], std3[2], (float*)out, kpad);
+    hipLaunchKernelGGL(im2col_kernel<float>, grid_for(total), dim3(256), 0, s, img, frame_map, frames, H, W, patch,
+                       mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], (float*)out, kpad);
   return sr::check_launch("sr_im2col_normalize");
+}
+
+extern "C" int64_t sr_frame_groups_workspace(int64_t frame_words, int n_frames) {
+  if (frame_words < 1 || frame_words > INT32_MAX || n_frames < 1 || n_frames > 65535) return 0;
+  // partials [n][chunks][2] and fingerprints [n][2] (uint64), cand [n] and equal [n] (int32)
+  const int64_t bytes = (int64_t)n_frames * ((int64_t)fg_chunks(frame_words) * 16 + 16 + 4 + 4);
+  return (bytes + 15) / 16 * 16;
+}
+
+extern "C" int sr_frame_groups(sr_stream_t stream, const void* frames, int64_t frame_words,
+                               int64_t frame_stride_words, int n_frames, const uint64_t* fp_override, int32_t* out,
+                               void* workspace) {
+  SR_CHECK(frames && out && workspace, SR_EINVAL, "sr_frame_groups: null pointer");
+  SR_CHECK(frame_words >= 1 && frame_words <= INT32_MAX && n_frames >= 1 && n_frames <= 65535, SR_EINVAL,
+           "sr_frame_groups: frame_words=%lld (1 .. 2^31 - 1), n_frames=%d (1 .. 65535)", (long long)frame_words,
+           n_frames);
+  SR_CHECK(n_frames == 1 || frame_stride_words >= frame_words, SR_EINVAL,
+           "sr_frame_groups: frame stride %lld below the frame's %lld words", (long long)frame_stride_words,
+           (long long)frame_words);
+  SR_CHECK(((uintptr_t)frames & 3) == 0 && ((uintptr_t)out & 3) == 0 && ((uintptr_t)workspace & 7) == 0 &&
+               ((uintptr_t)fp_override & 7) == 0,
+           SR_EINVAL, "sr_frame_groups: frames / out need 4-byte, workspace / fp_override 8-byte alignment");
+  hipStream_t s = (hipStream_t)stream;
+  const int chunks = fg_chunks(frame_words);
+  const uint32_t* fr = (const uint32_t*)frames;
+  uint64_t* partials = (uint64_t*)workspace;
+  uint64_t* fp = partials + (int64_t)n_frames * chunks * 2;
+  int32_t* cand = (int32_t*)(fp + (int64_t)n_frames * 2);
+  int32_t* equal = cand + n_frames;
+  const dim3 grid((unsigned)chunks, (unsigned)n_frames);
+  if (!fp_override)
+    hipLaunchKernelGGL(frame_fingerprint_kernel, grid, dim3(256), 0, s, fr, frame_words, frame_stride_words, chunks,
+                       partials);
+  hipLaunchKernelGGL(frame_candidate_kernel, dim3(1), dim3(256), 0, s, partials, chunks, fp_override, n_frames, fp,
+                     cand, equal);
+  hipLaunchKernelGGL(frame_compare_kernel, grid, dim3(256), 0, s, fr, frame_words, frame_stride_words, cand, equal);
+  hipLaunchKernelGGL(frame_rep_kernel, dim3((n_frames + 255) / 256), dim3(256), 0, s, cand, equal, n_frames, out);
+  return sr::check_launch("sr_frame_groups");
 }
 
 extern "C" int sr_set_special_tokens(sr_stream_t stream, float* x, int64_t ldx, int frames, int tokens_per_frame,

@@ -188,6 +188,10 @@ _PROTOS = {
     "sr_residual_layernorm": (_i32, [_vp, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _f32, _vp, _i64, _i32, _i32]),
     "sr_im2col_normalize": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, ctypes.POINTER(_f32),
                                    ctypes.POINTER(_f32), _vp, _i32]),
+    "sr_im2col_normalize_map": (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, ctypes.POINTER(_f32),
+                                       ctypes.POINTER(_f32), _vp, _i32]),
+    "sr_frame_groups_workspace": (_i64, [_i64, _i32]),
+    "sr_frame_groups": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
     "sr_set_special_tokens": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _i32]),
     "sr_copy_rows_f32": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32]),
     "sr_mul_cols": (_i32, [_vp, _i32, _vp, _i64, _vp, _vp, _i64, _i32, _i32]),

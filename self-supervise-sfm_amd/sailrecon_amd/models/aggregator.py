@@ -30,6 +30,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib, ops, runtime
+from ..frame_dedup import group_frames
 from ..layers import PatchEmbed
 from ..layers.block import Block
 from ..layers.rope import PositionGetter, RotaryPositionEmbedding2D
@@ -101,6 +102,10 @@ class Aggregator(nn.Module):
         # K|V of every global_reloc layer, kept in HBM (the reference round-trips it via the CPU)
         self.kv_cache = kv_cache
         self._kv_cache_layers: Optional[List[torch.Tensor]] = None
+        # (frames, distinct frames the DINO stack ran on) of the last _embed, and its cached tables
+        self.last_frame_groups: Optional[Tuple[int, int]] = None
+        self._rep_host: Optional[torch.Tensor] = None
+        self._dedup_tables = None
 
     # ------------------------------------------------------------------ construction
     def __build_patch_embed__(self, patch_embed, img_size, patch_size, num_register_tokens,
@@ -229,15 +234,27 @@ class Aggregator(nn.Module):
         kpad = -(-3 * ps * ps // kt) * kt
         misc = self._pack_misc(dtype, kpad)
         cols = ws.get("im2col", F_ * n_patch, kpad, dtype, dev)
-        ops.im2col_normalize(imgs, ps, cols, kpad)
         is_dino = hasattr(self.patch_embed, "blocks")
+        # ---- frame dedup: the DINO stack once per DISTINCT frame (frame_dedup.py).  U frames run on
+        # the compact stream xd [U*P, C]; DINO's final norm expands them into x by a row map
+        U, fmap, expand = F_, None, None
+        if is_dino and _DEDUP_FRAMES and F_ >= 2 and imgs.is_cuda:
+            fmap, expand = self._frame_groups(imgs, F_, P)
+            U = F_ if fmap is None else fmap.numel()
+        self.last_frame_groups = (F_, U)
+        xd = x if U == F_ else ws.get("x_dino", U * P, C, torch.float32, dev)
+        Rd = U * P
+        if fmap is None:
+            ops.im2col_normalize(imgs, ps, cols, kpad)
+        else:
+            ops.im2col_normalize(imgs, ps, cols, kpad, frame_map=fmap)  # the U distinct frames, no gather pass
         if is_dino:
             dino = self.patch_embed
             pos_tab = dino.pos_embed_for(H, W)  # [1 + n_patch, C] fp32
             row_add = pos_tab[1:]
         else:
             row_add = ws.get("zeros_pos", n_patch, C, torch.float32, dev).zero_()
-        ops.gemm(cols, misc["w_patch"], x, _lib.SR_EPI_PATCH, bias=misc["b_patch"], rows=F_ * n_patch,
+        ops.gemm(cols, misc["w_patch"], xd, _lib.SR_EPI_PATCH, bias=misc["b_patch"], rows=U * n_patch,
                  patch=dict(seg_rows=n_patch, seg_stride=P, seg_offset=psi, row_add=row_add), tag="gemm")
         if is_dino:
             nreg_d = dino.num_register_tokens
@@ -254,25 +271,46 @@ class Aggregator(nn.Module):
                 self._packed[key] = (dtab.detach().float().contiguous()[None],
                                      torch.zeros(F_, 1, dtype=torch.int32, device=dev))
             dtab, zero_t = self._packed[key]
-            ops.set_special_tokens(x, F_, P, dtab, zero_t)
+            ops.set_special_tokens(xd, U, P, dtab, zero_t)
             pending = []  # fc2 residual of block i folded into block i+1's LN1 (runtime.Pending)
             nblk = len(dino.blocks)
             for i, blk in enumerate(dino.blocks):
                 pb = blk.packed(dtype)
                 qs = runtime.q_prescale(pb)  # c*q rounded once by the QKV GEMM (runtime.q_prescale)
-                p = runtime.run_block(pb, x, 0, R, sc, runtime.frame_attend(pb, F_, P, tail_readable=True,
-                                                                            q_scaled=qs > 0),
+                p = runtime.run_block(pb, xd, 0, Rd, sc, runtime.frame_attend(pb, U, P, tail_readable=True,
+                                                                              q_scaled=qs > 0),
                                       runtime.qkv_params(pb, None, prescale=True), pending=pending,
                                       defer=i < nblk - 1, q_scale=qs)
                 if p is not None:
                     pending.append(p)
             assert not pending
-            ops.layernorm(x, dino.norm.weight, dino.norm.bias, dino.norm.eps, x)  # in place (row-local)
+            # in place (row-local); deduplicated: x row f*P + t = LN(xd row slot(f)*P + t), the expansion
+            ops.layernorm(xd, dino.norm.weight, dino.norm.bias, dino.norm.eps, x, rowmap=expand)
 
         # ---- aggregator special tokens, aggregator.py:287-299 (type by ORIGINAL frame index)
         ops.set_special_tokens(x, F_, P, misc["special"], ftype_t_fn())
         return x, sc
 
+    def _frame_groups(self, imgs: torch.Tensor, F_: int, P: int):
+        """The bit-identical frames among ``imgs`` [F_, 3, H, W] (ops.frame_groups; ONE small pinned
+        read-back and stream wait) -> (frame map int32 [U], row map int32 [F_*P]) on the device for
+        im2col and the expanding LayerNorm, or (None, None) when every frame is distinct."""
+        dev = imgs.device
+        rep_d = ops.frame_groups(imgs.view(F_, -1))
+        host = self._rep_host
+        if host is None or host.numel() < F_:
+            host = self._rep_host = torch.empty(max(F_, 64), dtype=torch.int32).pin_memory()
+        host[:F_].copy_(rep_d, non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()
+        rep = host[:F_].numpy().copy()
+        if (rep == np.arange(F_)).all():
+            return None, None
+        key = (rep.tobytes(), P, str(dev))
+        if self._dedup_tables is None or self._dedup_tables[0] != key:  # the same grouping as last time: keep
+            uniq, _, rowmap = group_frames(rep, P)
+            buf = runtime.to_device(torch.from_numpy(np.concatenate([uniq, rowmap])), dev)
+            self._dedup_tables = (key, buf[:len(uniq)], buf[len(uniq):])
+        return self._dedup_tables[1], self._dedup_tables[2]
 
     def forward(self, images: torch.Tensor, no_reloc_list: list, reloc_list: list,
                 fix_rank: Union[int, None] = None, *, outputs: str = "all"
@@ -952,6 +990,8 @@ _SHARD_TAIL = os.environ.get("SR_SHARD_TAIL", "0") == "1"
 _SHARD_CONCURRENT = os.environ.get("SR_SHARD_CONCURRENT", "1") != "0"
 # SR_CAMERA_ONLY=0 (A/B switch): forward(outputs="camera") behaves as outputs="all"
 _CAMERA_ONLY = os.environ.get("SR_CAMERA_ONLY", "1") != "0"
+# SR_DEDUP_FRAMES=0: the DINO stack runs on every frame, duplicates included (_embed, frame_dedup.py)
+_DEDUP_FRAMES = os.environ.get("SR_DEDUP_FRAMES", "1") != "0"
 # smallest query set (in 256-row x head workgroups) whose reloc attention runs split (A/B switch)
 _RELOC_SPLIT_MIN_WG = int(os.environ.get("SR_RELOC_SPLIT_MIN_WG", "2048"))
 

@@ -954,17 +954,69 @@ _MEAN = (0.485, 0.456, 0.406)  # aggregator.py:31-32
 _STD = (0.229, 0.224, 0.225)
 
 
-def im2col_normalize(img: Tensor, patch: int, out: Tensor, kpad: int, normalize: bool = True) -> None:
+def im2col_normalize(img: Tensor, patch: int, out: Tensor, kpad: int, normalize: bool = True,
+                     frame_map: Optional[Tensor] = None) -> None:
     """out[f*gh*gw + p][k] = patch p's pixel k of frame f ((x - mean) / std when ``normalize``,
-    aggregator.py:267; raw for a standalone PatchEmbed, patch_embed.py:78), K zero-padded."""
+    aggregator.py:267; raw for a standalone PatchEmbed, patch_embed.py:78), K zero-padded.
+    ``frame_map`` (device int32 [U], entries < F): output frame u reads frame frame_map[u]
+    (sr_im2col_normalize_map)."""
     if not img.is_contiguous() or img.dtype != torch.float32:
         raise ValueError("im2col: images must be contiguous fp32 [F,3,H,W]")
     F_, C_, H, W = img.shape
     mean = (ctypes.c_float * 3)(*(_MEAN if normalize else (0.0, 0.0, 0.0)))
     std = (ctypes.c_float * 3)(*(_STD if normalize else (1.0, 1.0, 1.0)))
+    if frame_map is not None:
+        if frame_map.dtype != torch.int32 or frame_map.dim() != 1 or not frame_map.is_contiguous() or \
+                frame_map.device != img.device:
+            raise ValueError("im2col: frame_map must be a contiguous int32 vector on the images' device")
+        rc = _lib.load().sr_im2col_normalize_map(_stream(img), dtype_code(out.dtype), _p(img), _p(frame_map),
+                                                 frame_map.numel(), H, W, patch, mean, std, _p(out), kpad)
+        check(rc, "sr_im2col_normalize_map")
+        return
     rc = _lib.load().sr_im2col_normalize(_stream(img), dtype_code(out.dtype), _p(img), F_, H, W, patch, mean, std,
                                          _p(out), kpad)
     check(rc, "sr_im2col_normalize")
+
+
+_FRAME_GROUPS_WS = {}  # (device, stream) -> workspace of sr_frame_groups
+
+
+def frame_groups_workspace_bytes(frame_words: int, n_frames: int) -> int:
+    return int(_lib.load().sr_frame_groups_workspace(frame_words, n_frames))
+
+
+def frame_groups(frames: Tensor, out: Optional[Tensor] = None, *, fp_override: Optional[Tensor] = None,
+                 workspace: Optional[Tensor] = None) -> Tensor:
+    """rep (device int32 [n]) of the bit-identical frames among ``frames`` (sr_frame_groups): a 2-D
+    view [n, words] of 4-byte elements with unit word stride (rows may start at any 4-byte address),
+    rep[f] = the first frame holding frame f's bits, or f.  Queued on the current stream; the caller
+    reads rep back.  ``fp_override`` (int64 [n, 2]): fingerprints to use instead of the computed
+    ones; ``workspace`` (uint8, >= frame_groups_workspace_bytes): default a cached one."""
+    if frames.dim() != 2 or frames.element_size() != 4 or frames.stride(1) != 1 or not frames.is_cuda:
+        raise ValueError("frame_groups: frames must be a device [n, words] view of 4-byte elements, unit word stride")
+    n, words = frames.shape
+    need = frame_groups_workspace_bytes(words, n)
+    if need <= 0:
+        raise ValueError(f"frame_groups: n={n} (1 .. 65535) or words={words} (1 .. 2^31 - 1) out of range")
+    if workspace is None:
+        key = _ws_stream_key(frames.device)
+        workspace = _FRAME_GROUPS_WS.get(key)
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty(need, device=frames.device, dtype=torch.uint8)
+            _FRAME_GROUPS_WS[key] = workspace
+    elif workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous():
+        raise ValueError(f"frame_groups: workspace must be contiguous uint8 of >= {need} bytes")
+    if out is None:
+        out = torch.empty(n, device=frames.device, dtype=torch.int32)
+    elif out.dtype != torch.int32 or out.numel() < n or not out.is_contiguous() or out.device != frames.device:
+        raise ValueError("frame_groups: out must be a contiguous device int32 [n]")
+    if fp_override is not None and (fp_override.dtype != torch.int64 or tuple(fp_override.shape) != (n, 2) or
+                                    not fp_override.is_contiguous() or fp_override.device != frames.device):
+        raise ValueError("frame_groups: fp_override must be a contiguous device int64 [n, 2]")
+    rc = _lib.load().sr_frame_groups(_stream(frames), _p(frames), words, frames.stride(0) if n > 1 else words, n,
+                                     _p(fp_override), _p(out), _p(workspace))
+    check(rc, "sr_frame_groups")
+    return out
 
 
 def set_special_tokens(x: Tensor, frames: int, tokens_per_frame: int, table: Tensor, type_of_frame: Tensor) -> None:
