@@ -922,6 +922,70 @@ int64_t sr_corres_sample_workspace(int n_pairs, int max_m);
  * for a null pointer, n_points <= 0, n_pairs <= 0, max_m <= 0 or an undersized workspace. */
 int sr_corres_sample(sr_stream_t stream, const sr_corres_desc* desc);
 
+/* ------------------------------------------------------------------------------------------
+ * Scoring poses (ABI 1.9): what the reference's demos hand to their `eval` package
+ * (train/demo_imc_forward.py:109-128: eval.utils.geometry, eval.utils.eval_utils; the package is
+ * absent from the reference tree) on the relative pose of compute_relative_pose
+ * (train/utils/geometry.py:240-282), T_j T_i^-1, in closed form.  Poses are world-to-camera [R|t]
+ * (OpenCV), fp32 row-major, view k at base + k * stride floats, stride 12 (3x4) or 16 (4x4); the R
+ * block is used as given.  Definitions: DESIGN.md "Scoring poses", csrc/sr_pose_eval.hip.
+ *   R_ij = R_j R_i^T, t_ij = t_j - R_ij t_i
+ *   rot   = atan2(|(E21 - E12, E02 - E20, E10 - E01)| / 2, (tr E - 1) / 2) in degrees, E = (R^gt_ij)^T R^pr_ij
+ *   trans = atan2(|a x b|, a.b) in degrees, a = t^gt_ij, b = t^pr_ij (|a.b| with trans_ambiguity);
+ *           0 if a.a == 0 and b.b == 0, 180 (90 with ambiguity) if exactly one of them is 0
+ *   hist[row][k], rows rot / trans / max(rot, trans), n_bins + 2 slots each: k < n_bins counts
+ *           k <= fl32(err / bin_deg) < k + 1, slot n_bins the larger errors, slot n_bins + 1 the
+ *           non-finite pairs: a NaN or Inf in one of the four poses (a test on the bits), an index
+ *           outside [0, n_views) (nothing is loaded through it), or an error that evaluates to a
+ *           non-finite value; their rot_err / trans_err are NaN.  Integer atomics only.
+ *   a list entry with i == j scores rot = trans = 0 (T_i T_i^-1 is the identity) unless non-finite
+ * ------------------------------------------------------------------------------------------ */
+typedef struct sr_pose_pairs_desc {
+  const float* pred;        /* [n_views][pred_stride] */
+  const float* gt;          /* [n_views][gt_stride] */
+  int pred_stride, gt_stride;
+  int n_views;              /* 1 .. 65535 (pair counts stay inside uint32) */
+  int n_pairs;              /* entries of pair_i / pair_j; ignored for all pairs */
+  const int32_t* pair_i;    /* both NULL: all i < j, pair p = i (2 n_views - i - 1) / 2 + (j - i - 1) */
+  const int32_t* pair_j;    /* else [n_pairs] each: any order, i == j and repeats allowed */
+  int trans_ambiguity;
+  int n_bins;               /* 1 .. 1024 */
+  float bin_deg;            /* > 0 */
+  uint32_t* hist;           /* [3][n_bins + 2]; zeroed by the call, on the stream */
+  float* rot_err;           /* [pairs] degrees, or NULL */
+  float* trans_err;         /* [pairs] degrees, or NULL */
+} sr_pose_pairs_desc;
+
+/* One clearing launch and one pair kernel (a 64 x 64 tiling of the triangle with both tiles' poses
+ * staged in LDS, or a walk of the list), asynchronous and allocation-free.  SR_EINVAL for a null
+ * pointer, n_views outside [1, 65535], a stride other than 12 or 16, n_bins outside [1, 1024],
+ * bin_deg not positive and finite, exactly one of pair_i / pair_j, or a list with n_pairs <= 0. */
+int sr_pose_pair_errors(sr_stream_t stream, const sr_pose_pairs_desc* desc);
+
+/* Similarity alignment of the camera centres c_k = -R_k^T t_k (Umeyama): gt ~ s R pred + t over all
+ * views, s = 1 unless with_scale.  Means, variance and covariance in fp64 from the fp32 inputs in a
+ * fixed order (bit-stable), SVD of the 3x3 covariance in fp64 with the det(U) det(V) < 0 sign fix;
+ * singular vectors of zero singular values are completed to an orthonormal basis.
+ *   out[0] scale, out[1..9] R row-major, out[10..12] t, out[13] ate = sqrt(mean |gt - (s R pred + t)|^2)
+ *   status bit 1 (value 2): the covariance has rank < 2 (sigma_2 <= 1e-12 sigma_1), the rotation is
+ *          not unique; bit 0 (value 1): the predicted centres coincide (zero variance): s = 1,
+ *          R = I, t = the difference of the means, and bit 1 is set too */
+typedef struct sr_pose_align_desc {
+  const float* pred;        /* [n_views][pred_stride] */
+  const float* gt;          /* [n_views][gt_stride] */
+  int pred_stride, gt_stride;
+  int n_views;              /* 1 .. 65535 */
+  int with_scale;
+  double* out;              /* [14] */
+  int32_t* status;          /* [1] */
+  double* err;              /* [n_views] per-view |gt - (s R pred + t)|, or NULL */
+} sr_pose_align_desc;
+
+/* One workgroup looping over the views, asynchronous and allocation-free.  SR_EINVAL for a null
+ * pred / gt / out / status, n_views outside [1, 65535], a stride other than 12 or 16 or an fp64
+ * buffer that is not 8-byte aligned. */
+int sr_pose_align(sr_stream_t stream, const sr_pose_align_desc* desc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@
 //                           compares them with the ctypes mirror in sailrecon_amd/_lib.py)
 //   abi_host_check layout corres   the same for the structs of sr_corres_sample (ABI 1.6), apart:
 //                           tests/test_debug_build.py pins the set the plain mode prints
+//   abi_host_check layout pose_eval   the same for the structs of sr_pose_pair_errors / sr_pose_align (ABI 1.9)
 //   abi_host_check check    the validation sweep; exit 0 iff every call returned what it should
 #include <cstddef>
 #include <cstdio>
@@ -121,6 +122,24 @@ void layout_corres() {
           FIELD(sr_corres_desc, src_coords), FIELD(sr_corres_desc, dst_coords), FIELD(sr_corres_desc, src_depth),
           FIELD(sr_corres_desc, dst_depth), FIELD(sr_corres_desc, index), FIELD(sr_corres_desc, total),
           FIELD(sr_corres_desc, n_valid), FIELD(sr_corres_desc, workspace), FIELD(sr_corres_desc, workspace_doubles)));
+  std::printf("}\n");
+}
+
+void layout_pose_eval() {
+  const char* sep = "";
+  std::printf("{");
+  STRUCT(sr_pose_pairs_desc,
+         (FIELD(sr_pose_pairs_desc, pred), FIELD(sr_pose_pairs_desc, gt), FIELD(sr_pose_pairs_desc, pred_stride),
+          FIELD(sr_pose_pairs_desc, gt_stride), FIELD(sr_pose_pairs_desc, n_views), FIELD(sr_pose_pairs_desc, n_pairs),
+          FIELD(sr_pose_pairs_desc, pair_i), FIELD(sr_pose_pairs_desc, pair_j),
+          FIELD(sr_pose_pairs_desc, trans_ambiguity), FIELD(sr_pose_pairs_desc, n_bins),
+          FIELD(sr_pose_pairs_desc, bin_deg), FIELD(sr_pose_pairs_desc, hist), FIELD(sr_pose_pairs_desc, rot_err),
+          FIELD(sr_pose_pairs_desc, trans_err)));
+  STRUCT(sr_pose_align_desc,
+         (FIELD(sr_pose_align_desc, pred), FIELD(sr_pose_align_desc, gt), FIELD(sr_pose_align_desc, pred_stride),
+          FIELD(sr_pose_align_desc, gt_stride), FIELD(sr_pose_align_desc, n_views),
+          FIELD(sr_pose_align_desc, with_scale), FIELD(sr_pose_align_desc, out), FIELD(sr_pose_align_desc, status),
+          FIELD(sr_pose_align_desc, err)));
   std::printf("}\n");
 }
 
@@ -424,6 +443,74 @@ void check() {
     b = cd, b.n_pairs = 70000, b.workspace_doubles = sr_corres_sample_workspace(70000, 313600);
     expect("sr_corres_sample 70000 pairs", sr_corres_sample(nullptr, &b), false);
   }
+  expect("sr_pose_pair_errors null", sr_pose_pair_errors(nullptr, nullptr), false);
+  expect("sr_pose_align null", sr_pose_align(nullptr, nullptr), false);
+  {  // ABI 1.9: every rejection the header lists, then the two pair sets and both strides up to the launch
+    sr_pose_pairs_desc pd{};
+    pd.pred = fake<float>(0), pd.gt = fake<float>(1), pd.pred_stride = 12, pd.gt_stride = 16, pd.n_views = 4096;
+    pd.trans_ambiguity = 1, pd.n_bins = 180, pd.bin_deg = 1.f, pd.hist = fake<uint32_t>(2);
+    expect("sr_pose_pair_errors all pairs, histogram only", sr_pose_pair_errors(nullptr, &pd), true);
+    sr_pose_pairs_desc b = pd;
+    b.rot_err = fake<float>(3), b.trans_err = fake<float>(4), b.n_views = 65535, b.n_bins = 1024;
+    expect("sr_pose_pair_errors 65535 views, 1024 bins", sr_pose_pair_errors(nullptr, &b), true);
+    b = pd, b.pair_i = fake<int32_t>(5), b.pair_j = fake<int32_t>(6), b.n_pairs = 2147483647;
+    expect("sr_pose_pair_errors list of 2^31 - 1", sr_pose_pair_errors(nullptr, &b), true);
+    b.n_pairs = 0;
+    expect("sr_pose_pair_errors empty list", sr_pose_pair_errors(nullptr, &b), false);
+    b = pd, b.pair_i = fake<int32_t>(5), b.n_pairs = 7;
+    expect("sr_pose_pair_errors pair_i without pair_j", sr_pose_pair_errors(nullptr, &b), false);
+    b = pd, b.pair_j = fake<int32_t>(6), b.n_pairs = 7;
+    expect("sr_pose_pair_errors pair_j without pair_i", sr_pose_pair_errors(nullptr, &b), false);
+    b = pd, b.pred = nullptr;
+    expect("sr_pose_pair_errors null pred", sr_pose_pair_errors(nullptr, &b), false);
+    b = pd, b.gt = nullptr;
+    expect("sr_pose_pair_errors null gt", sr_pose_pair_errors(nullptr, &b), false);
+    b = pd, b.hist = nullptr;
+    expect("sr_pose_pair_errors null hist", sr_pose_pair_errors(nullptr, &b), false);
+    b = pd, b.n_views = 0;
+    expect("sr_pose_pair_errors 0 views", sr_pose_pair_errors(nullptr, &b), false);
+    b = pd, b.n_views = 65536;
+    expect("sr_pose_pair_errors 65536 views", sr_pose_pair_errors(nullptr, &b), false);
+    b = pd, b.pred_stride = 9;
+    expect("sr_pose_pair_errors stride 9", sr_pose_pair_errors(nullptr, &b), false);
+    b = pd, b.gt_stride = 0;
+    expect("sr_pose_pair_errors stride 0", sr_pose_pair_errors(nullptr, &b), false);
+    b = pd, b.n_bins = 0;
+    expect("sr_pose_pair_errors 0 bins", sr_pose_pair_errors(nullptr, &b), false);
+    b = pd, b.n_bins = 1025;
+    expect("sr_pose_pair_errors 1025 bins", sr_pose_pair_errors(nullptr, &b), false);
+    b = pd, b.bin_deg = 0.f;
+    expect("sr_pose_pair_errors bin_deg 0", sr_pose_pair_errors(nullptr, &b), false);
+    b = pd, b.bin_deg = -1.f;
+    expect("sr_pose_pair_errors bin_deg -1", sr_pose_pair_errors(nullptr, &b), false);
+    const uint32_t nan_bits = 0x7fc00000u;
+    b = pd, std::memcpy(&b.bin_deg, &nan_bits, sizeof(nan_bits));
+    expect("sr_pose_pair_errors bin_deg NaN", sr_pose_pair_errors(nullptr, &b), false);
+
+    sr_pose_align_desc ad{};
+    ad.pred = fake<float>(0), ad.gt = fake<float>(1), ad.pred_stride = 16, ad.gt_stride = 12, ad.n_views = 65535;
+    ad.with_scale = 1, ad.out = fake<double>(2), ad.status = fake<int32_t>(3);
+    expect("sr_pose_align 65535 views", sr_pose_align(nullptr, &ad), true);
+    sr_pose_align_desc c = ad;
+    c.err = fake<double>(4), c.n_views = 1, c.with_scale = 0;
+    expect("sr_pose_align one view, per-view errors", sr_pose_align(nullptr, &c), true);
+    c = ad, c.pred = nullptr;
+    expect("sr_pose_align null pred", sr_pose_align(nullptr, &c), false);
+    c = ad, c.gt = nullptr;
+    expect("sr_pose_align null gt", sr_pose_align(nullptr, &c), false);
+    c = ad, c.out = nullptr;
+    expect("sr_pose_align null out", sr_pose_align(nullptr, &c), false);
+    c = ad, c.status = nullptr;
+    expect("sr_pose_align null status", sr_pose_align(nullptr, &c), false);
+    c = ad, c.n_views = 0;
+    expect("sr_pose_align 0 views", sr_pose_align(nullptr, &c), false);
+    c = ad, c.n_views = 65536;
+    expect("sr_pose_align 65536 views", sr_pose_align(nullptr, &c), false);
+    c = ad, c.gt_stride = 13;
+    expect("sr_pose_align stride 13", sr_pose_align(nullptr, &c), false);
+    c = ad, c.out = (double*)((char*)fake(2) + 4);
+    expect("sr_pose_align out % 8", sr_pose_align(nullptr, &c), false);
+  }
   expect("sr_pose_decode_f32 null", sr_pose_decode_f32(nullptr, nullptr, 9, 0, 518, 518, nullptr, nullptr), false);
   expect("sr_copy_rows_f32 null", sr_copy_rows_f32(nullptr, nullptr, 0, nullptr, 0, nullptr, 0, 0), false);
   expect("sr_conv3x3_f32 null", sr_conv3x3_f32(nullptr, nullptr, 1, 8, 8, 32, 1, 0, nullptr, 32, SR_EPI_BIAS, &ep, nullptr, 32, nullptr), false);
@@ -493,6 +580,8 @@ int main(int argc, char** argv) {
   if (mode == "layout") {
     if (argc > 2 && std::string(argv[2]) == "corres")
       layout_corres();
+    else if (argc > 2 && std::string(argv[2]) == "pose_eval")
+      layout_pose_eval();
     else
       layout();
     return 0;

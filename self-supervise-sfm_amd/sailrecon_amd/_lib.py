@@ -142,6 +142,23 @@ class CorresDesc(ctypes.Structure):
     ]
 
 
+class PosePairsDesc(ctypes.Structure):
+    """sr_pose_pairs_desc (include/sfm_amd.h)."""
+    _fields_ = [
+        ("pred", _vp), ("gt", _vp), ("pred_stride", _i32), ("gt_stride", _i32), ("n_views", _i32), ("n_pairs", _i32),
+        ("pair_i", _vp), ("pair_j", _vp), ("trans_ambiguity", _i32), ("n_bins", _i32), ("bin_deg", _f32),
+        ("hist", _vp), ("rot_err", _vp), ("trans_err", _vp),
+    ]
+
+
+class PoseAlignDesc(ctypes.Structure):
+    """sr_pose_align_desc (include/sfm_amd.h)."""
+    _fields_ = [
+        ("pred", _vp), ("gt", _vp), ("pred_stride", _i32), ("gt_stride", _i32), ("n_views", _i32),
+        ("with_scale", _i32), ("out", _vp), ("status", _vp), ("err", _vp),
+    ]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "sr_last_error": (ctypes.c_char_p, []),
@@ -237,6 +254,8 @@ _PROTOS = {
     "sr_resize_crop_chw_f32": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "sr_corres_sample_workspace": (_i64, [_i32, _i32]),
     "sr_corres_sample": (_i32, [_vp, ctypes.POINTER(CorresDesc)]),
+    "sr_pose_pair_errors": (_i32, [_vp, ctypes.POINTER(PosePairsDesc)]),
+    "sr_pose_align": (_i32, [_vp, ctypes.POINTER(PoseAlignDesc)]),
 }
 EXPORTED = tuple(_PROTOS)
 

@@ -1330,6 +1330,77 @@ def corres_sample(pairs, uniforms: Tensor, min_conf: float, *, want_index: bool 
     return out
 
 
+# ---------------------------------------------------------------- scoring poses (utils/pose_eval.py)
+def _pose_views(t: Tensor, name: str) -> int:
+    """Floats per view (12 or 16) of a contiguous fp32 device tensor [N, 3, 4] / [N, 4, 4]."""
+    if not isinstance(t, Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous fp32 device tensor")
+    if t.dim() != 3 or t.shape[0] == 0 or tuple(t.shape[1:]) not in ((3, 4), (4, 4)):
+        raise ValueError(f"{name} must be [N, 3, 4] or [N, 4, 4], got {tuple(t.shape)}")
+    return 4 * t.shape[1]
+
+
+def pose_pair_errors(pred: Tensor, gt: Tensor, hist: Tensor, *, bin_deg: float, trans_ambiguity: bool = True,
+                     pair_i: Optional[Tensor] = None, pair_j: Optional[Tensor] = None,
+                     rot_err: Optional[Tensor] = None, trans_err: Optional[Tensor] = None) -> None:
+    """sr_pose_pair_errors: relative rotation / translation errors (degrees) of all i < j or of the
+    (pair_i, pair_j) int32 list into ``hist`` [3, n_bins + 2] (int32 storage of the uint32 counts,
+    zeroed by the call) and, if given, the per-pair fp32 arrays."""
+    d = _lib.PosePairsDesc()
+    d.pred_stride, d.gt_stride = _pose_views(pred, "pred"), _pose_views(gt, "gt")
+    n = pred.shape[0]
+    if gt.shape[0] != n:
+        raise ValueError(f"gt has {gt.shape[0]} views, pred has {n}")
+    if hist.dtype != torch.int32 or hist.dim() != 2 or hist.shape[0] != 3 or hist.shape[1] < 3 or not hist.is_contiguous():
+        raise ValueError(f"hist must be a contiguous int32 [3, n_bins + 2] tensor, got {hist.dtype} {tuple(hist.shape)}")
+    if (pair_i is None) != (pair_j is None):
+        raise ValueError("pair_i and pair_j go together")
+    n_pairs = n * (n - 1) // 2
+    if pair_i is not None:
+        for name, t in (("pair_i", pair_i), ("pair_j", pair_j)):
+            if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() == 0:
+                raise ValueError(f"{name} must be a contiguous non-empty int32 vector")
+        if pair_i.numel() != pair_j.numel():
+            raise ValueError(f"pair_i has {pair_i.numel()} entries, pair_j has {pair_j.numel()}")
+        n_pairs = pair_i.numel()
+    tensors = [("gt", gt), ("hist", hist), ("pair_i", pair_i), ("pair_j", pair_j)]
+    for name, t in (("rot_err", rot_err), ("trans_err", trans_err)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n_pairs):
+            raise ValueError(f"{name} must be a contiguous fp32 tensor of {n_pairs} entries")
+        tensors.append((name, t))
+    for name, t in tensors:
+        if t is not None and t.device != pred.device:
+            raise ValueError(f"{name} must live on {pred.device}")
+    d.pred, d.gt, d.n_views, d.n_pairs = _p(pred), _p(gt), n, min(n_pairs, 2 ** 31 - 1)
+    d.pair_i, d.pair_j, d.trans_ambiguity = _p(pair_i), _p(pair_j), int(bool(trans_ambiguity))
+    d.n_bins, d.bin_deg, d.hist = hist.shape[1] - 2, float(bin_deg), _p(hist)
+    d.rot_err, d.trans_err = _p(rot_err), _p(trans_err)
+    check(_lib.load().sr_pose_pair_errors(_stream(pred), ctypes.byref(d)), "sr_pose_pair_errors")
+
+
+def pose_align(pred: Tensor, gt: Tensor, out: Tensor, status: Tensor, *, with_scale: bool = True,
+               err: Optional[Tensor] = None) -> None:
+    """sr_pose_align: the Umeyama fit gt ~ s R pred + t of the camera centres into ``out`` [14] fp64
+    (scale, R row-major, t, ate), ``status`` [1] int32 and, if given, ``err`` [N] fp64."""
+    d = _lib.PoseAlignDesc()
+    d.pred_stride, d.gt_stride = _pose_views(pred, "pred"), _pose_views(gt, "gt")
+    n = pred.shape[0]
+    if gt.shape[0] != n:
+        raise ValueError(f"gt has {gt.shape[0]} views, pred has {n}")
+    if out.dtype != torch.float64 or out.numel() != 14 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous fp64 tensor of 14 entries")
+    if status.dtype != torch.int32 or status.numel() != 1:
+        raise ValueError("status must be an int32 tensor of one entry")
+    if err is not None and (err.dtype != torch.float64 or err.numel() != n or not err.is_contiguous()):
+        raise ValueError(f"err must be a contiguous fp64 tensor of {n} entries")
+    for name, t in (("gt", gt), ("out", out), ("status", status), ("err", err)):
+        if t is not None and t.device != pred.device:
+            raise ValueError(f"{name} must live on {pred.device}")
+    d.pred, d.gt, d.n_views, d.with_scale = _p(pred), _p(gt), n, int(bool(with_scale))
+    d.out, d.status, d.err = _p(out), _p(status), _p(err)
+    check(_lib.load().sr_pose_align(_stream(pred), ctypes.byref(d)), "sr_pose_align")
+
+
 # ---------------------------------------------------------------- training step (SURVEY §8(f) rank 4)
 _TRAIN_WS = {}  # ((device, stream), name) -> fp32 workspace
 
