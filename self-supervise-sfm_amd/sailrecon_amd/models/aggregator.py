@@ -23,6 +23,8 @@ from __future__ import annotations
 
 import logging
 import os
+from dataclasses import dataclass
+from functools import partial
 from typing import Dict, List, Optional, Tuple, Union
 
 import numpy as np
@@ -40,6 +42,38 @@ logger = logging.getLogger(__name__)
 
 _RESNET_MEAN = [0.485, 0.456, 0.406]
 _RESNET_STD = [0.229, 0.224, 0.225]
+
+
+@dataclass
+class _LayerCtx:
+    """What one forward's alternating layers share, then (``l`` on) what the caller sets per layer.  x orders
+    each batch item's frames as [Na_l anchors ; Nq_l queries] of P rows each; ``a_counts`` = anchor frames
+    per rank of the ``G`` ranks of ``group`` (this one: r); Pp = subsample rows per anchor frame."""
+    x: torch.Tensor
+    sc: runtime.BlockScratch
+    P: int
+    Pp: int
+    rope: Optional[tuple]
+    posctx: dict
+    dtype: torch.dtype
+    dev: object
+    Na_l: int
+    Nq_l: int
+    group: object = None
+    G: int = 1
+    r: int = 0
+    a_counts: tuple = (0,)
+    rowmap_t: Optional[torch.Tensor] = None       # [depth, B, Na_l * Pp] subsample rows of x, where wanted
+    fill_cache: bool = False                      # keep every layer's anchor-subsample K|V (kv_cache)
+    l: int = 0
+    pr: Optional[runtime.PackedBlock] = None      # global_reloc block (query rows)
+    pg: Optional[runtime.PackedBlock] = None      # global block (anchor rows)
+    defer: bool = False                           # leave the blocks' fc2 residuals pending
+
+    def rows(self, b: int) -> Tuple[int, int, int]:
+        """(a0, q0, q1): batch item b's anchor rows [a0, q0) and query rows [q0, q1) of x."""
+        a0 = b * (self.Na_l + self.Nq_l) * self.P
+        return a0, a0 + self.Na_l * self.P, a0 + (self.Na_l + self.Nq_l) * self.P
 
 
 class Aggregator(nn.Module):
@@ -364,9 +398,6 @@ class Aggregator(nn.Module):
         psi = self.patch_start_idx
         P = n_patch + psi
         F_ = B * S_l
-        R = F_ * P
-        ws = self._ws
-        hidden = self.frame_blocks[0].mlp.fc1.out_features
 
         # ---- internal (local) frame order: anchors then queries, per batch item
         order = my_anchors + my_queries
@@ -419,7 +450,9 @@ class Aggregator(nn.Module):
         if fill_cache:
             self._kv_cache_layers = [None] * self.depth
         rope = self.rope.tables(C // nh, max(gh, gw) + 1, dev) if self.rope is not None else None
-        posctx = dict(tokens_per_frame=P, patch_start=psi, grid_w=gw)
+        ctx = _LayerCtx(x=x, sc=sc, P=P, Pp=Pp, rope=rope, posctx=dict(tokens_per_frame=P, patch_start=psi, grid_w=gw),
+                        dtype=dtype, dev=dev, Na_l=Na_l, Nq_l=Nq_l, group=group, G=G, r=r, a_counts=a_counts,
+                        rowmap_t=rowmap_t, fill_cache=fill_cache)
 
         # ---- outputs (this rank's query frames)
         out_maps: Dict[int, torch.Tensor] = {}
@@ -435,43 +468,26 @@ class Aggregator(nn.Module):
         # ---- alternating layers, aggregator.py:339-423
         pending = []  # the global / reloc blocks' fc2 residuals, folded into the next frame block's LN1
         for l in range(self.depth):
-            pb = self.frame_blocks[l].packed(dtype)
-            runtime.run_block(pb, x, 0, R, sc, runtime.frame_attend(pb, F_, P, tail_readable=True, q_scaled=_qs(pb)),
-                              runtime.qkv_params(pb, rope, prescale=True, pos_row_base=0, **posctx), pending=pending,
-                              q_scale=runtime.q_prescale(pb))
+            self._frame_block(ctx, l, F_, pending)
             if l in out_maps and Nq_l > 0:  # frame half of the intermediate, :403-413
-                for b in range(B):
-                    ops.copy_rows(out_maps[l][b].view(Nq_l * P, 2 * C)[:, :C],
-                                  x[b * S_l * P + Na_l * P:(b + 1) * S_l * P], Nq_l * P)
+                self._copy_query_half(ctx, out_maps[l], 0)
             if l == self.depth - 1:  # :414-423 frame half
                 ops.copy_rows(cam_flat[:, :C], x, B * Na_l, rowmap=anchor_rows0)
                 if camera:
                     ops.copy_rows(qcam_flat[:, :C], x, B * Nq_l, rowmap=query_rows0)
-            pr = self.global_reloc_blocks[l].packed(dtype)
-            pg = self.global_blocks[l].packed(dtype)
+            ctx.l, ctx.pr, ctx.pg = l, self.global_reloc_blocks[l].packed(dtype), self.global_blocks[l].packed(dtype)
             # the next reader of x after this layer's global / reloc blocks is the next frame block's LN1,
             # unless an output map or the camera tokens copy x first
-            defer = l + 1 < self.depth and l not in out_maps and not fill_cache and \
-                os.environ.get("SR_CONCURRENT_STACKS", "0") != "1"
+            ctx.defer = l + 1 < self.depth and l not in out_maps and not fill_cache and not _concurrent_stacks()
             if camera and l == self.depth - 1:
                 # x is dead after this layer: only the camera rows' tails run, on a compact stream
                 for b in range(B):
-                    a0, q0, q1 = b * S_l * P, b * S_l * P + Na_l * P, (b + 1) * S_l * P
-                    self._layer_global_camera(pr, pg, x, sc, rowmap_t[l, b], Pp, a0, q0, q1, Na_l, Nq_l, P, rope,
-                                              posctx, dtype, dev, anchor_rows0[b * Na_l:(b + 1) * Na_l],
-                                              query_rows0[b * Nq_l:(b + 1) * Nq_l],
-                                              cam_flat[b * Na_l:(b + 1) * Na_l, C:],
-                                              qcam_flat[b * Nq_l:(b + 1) * Nq_l, C:])
+                    self._layer_global_camera(ctx, b, anchor_rows0, query_rows0, cam_flat, qcam_flat)
                 break
             for b in range(B):
-                a0, q0, q1 = b * S_l * P, b * S_l * P + Na_l * P, (b + 1) * S_l * P
-                pending += self._layer_global(pr, pg, x, sc, rowmap_t[l, b] if need_sub else None, Pp, a0, q0, q1,
-                                              Nq_l, P, rope, posctx, dtype, dev, group, G, r, a_counts, need_sub,
-                                              cache_layer=l if fill_cache else None, defer=defer)
+                pending += self._layer_global(ctx, b)
             if l in out_maps and Nq_l > 0:  # reloc half
-                for b in range(B):
-                    ops.copy_rows(out_maps[l][b].view(Nq_l * P, 2 * C)[:, C:],
-                                  x[b * S_l * P + Na_l * P:(b + 1) * S_l * P], Nq_l * P)
+                self._copy_query_half(ctx, out_maps[l], 1)
             if l == self.depth - 1:
                 ops.copy_rows(cam_flat[:, C:], x, B * Na_l, rowmap=anchor_rows0)
 
@@ -536,35 +552,24 @@ class Aggregator(nn.Module):
         psi = self.patch_start_idx
         P = gh * gw + psi
         F_ = S
-        R = F_ * P
-        n_sub = self._kv_cache_layers[0].shape[0]
         imgs = images.reshape(F_, 3, H, W).float().contiguous()
         x, sc = self._embed(imgs, F_, H, W, ftype_t_fn=lambda: torch.full((F_,), 2, device=dev, dtype=torch.int32),
                             dtype=dtype)
         rope = self.rope.tables(C // nh, max(gh, gw) + 1, dev) if self.rope is not None else None
-        posctx = dict(tokens_per_frame=P, patch_start=psi, grid_w=gw)
+        # every frame is a query: no anchor rows, no subsample of its own
+        ctx = _LayerCtx(x=x, sc=sc, P=P, Pp=0, rope=rope, posctx=dict(tokens_per_frame=P, patch_start=psi, grid_w=gw),
+                        dtype=dtype, dev=dev, Na_l=0, Nq_l=F_)
         out_maps = {l: torch.empty(1, S, P, 2 * C, device=dev, dtype=torch.float32) for l in self.intermediate_layer_idx}
         for l in range(self.depth):
-            pb = self.frame_blocks[l].packed(dtype)
-            runtime.run_block(pb, x, 0, R, sc, runtime.frame_attend(pb, F_, P, tail_readable=True, q_scaled=_qs(pb)),
-                              runtime.qkv_params(pb, rope, prescale=True, pos_row_base=0, **posctx),
-                              q_scale=runtime.q_prescale(pb))
+            self._frame_block(ctx, l, F_)
             if l in out_maps:
-                ops.copy_rows(out_maps[l][0].view(R, 2 * C)[:, :C], x, R)
-            pr = self.global_reloc_blocks[l].packed(dtype)
-            kv = self._kv_cache_layers[l]
-
-            def attend_cached(qkv, o, kv=kv, pr=pr):
-                ops.attention(qkv[:, 0:C], kv[:, 0:C], kv[:, C:2 * C], o, heads=pr.heads, head_dim=pr.head_dim,
-                              batch=F_, lq=P, q_bstride=P, l0=n_sub, k0_bstride=0, k1=qkv[:, C:2 * C],
-                              v1=qkv[:, 2 * C:3 * C], l1=P, k1_bstride=P, tag="attn_reloc",
-                              key_norm_max=runtime.key_norm_bound(pr),
-                              query_norm_max=runtime.query_norm_bound(pr), q_scaled=_qs(pr))
-            runtime.run_block(pr, x, 0, R, sc, attend_cached,
-                              runtime.qkv_params(pr, rope, prescale=True, pos_row_base=0, **posctx),
-                              q_scale=runtime.q_prescale(pr))
+                self._copy_query_half(ctx, out_maps[l], 0)
+            ctx.pr = pr = self.global_reloc_blocks[l].packed(dtype)
+            # the cache is a clone(), not a padded Workspace buffer: its tail is not declared readable
+            runtime.run_block(pr, x, 0, F_ * P, sc, partial(self._reloc_one_launch, ctx, self._kv_cache_layers[l]),
+                              self._epi(ctx, pr, 0), q_scale=runtime.q_prescale(pr))
             if l in out_maps:
-                ops.copy_rows(out_maps[l][0].view(R, 2 * C)[:, C:], x, R)
+                self._copy_query_half(ctx, out_maps[l], 1)
         assert self.depth - 1 in out_maps, \
             f"Please make sure the last layer ({self.depth - 1}) is in the output_dict: {out_maps.keys()}"
         output_dict: Dict[int, torch.Tensor] = dict(out_maps)
@@ -572,228 +577,66 @@ class Aggregator(nn.Module):
         return output_dict, self.patch_start_idx
 
     # ------------------------------------------------------------------ stacks
-    def _layer_global(self, pr, pg, x, sc, rowmap, Pp, a0, q0, q1, Nq_l, P, rope, posctx, dtype, dev,
-                      group, G, r, a_counts, need_sub, cache_layer=None, defer=False) -> list:
-        """global_reloc (queries, aggregator.py:672-741) + global (anchors, :743-769) blocks of
-        one layer for one batch item.  With G > 1 the anchor K/V and the anchor-subsample K/V
-        are gathered asynchronously (``gather_rows``; ``a_counts`` = anchor frames per rank):
-        the subsample K/V behind the query-side QKV GEMM, the anchor K/V behind the whole reloc
-        block and the local-anchor attention pass.  ``defer``: the two blocks' fc2 residuals are
-        returned as runtime.Pending updates for the next frame block's LN1 (else [])."""
-        out = []
+    def _epi(self, ctx: _LayerCtx, pb, row_base: int) -> Optional[dict]:
+        """QKV epilogue of block ``pb`` over x rows from ``row_base`` on (its Q block leaves as c*q)."""
+        return runtime.qkv_params(pb, ctx.rope, prescale=True, pos_row_base=row_base, **ctx.posctx)
 
-        def keep(p):
-            if p is not None:
-                out.append(p)
-        C = pg.dim
-        ws = self._ws
-        La_l = q0 - a0                 # local anchor tokens
-        La = sum(a_counts) * P         # all anchor tokens
-        n_sub = (q0 - a0) // P * Pp    # local anchor-subsample rows
-        n_sub_all = sum(a_counts) * Pp
-        work_sub, work_kv = [], []
-        paired = G == 1 and self._paired_attention(pr, pg, dtype, Nq_l * P, q0 - a0, n_sub_all)
-        # paired: the subsample K/V projection joins the queries' and anchors' QKV GEMMs in one
-        # grouped launch below (its LayerNorm still reads x here, before the global block updates it)
-        defer_kv = paired and cache_layer is None and need_sub
-        if need_sub:
-            # anchor-subsample K/V (reads x before the global block updates the anchors)
-            xn_sub = ws.get("xn_sub", n_sub, C, dtype, dev)
-            if G > 1:  # separate send buffer: no aliasing between collective input and output
-                kv_sub = ws.get("kv_sub_loc", n_sub, 2 * C, dtype, dev)
-                kv_sub_all = ws.get("kv_sub", n_sub_all, 2 * C, dtype, dev)
-            else:
-                kv_sub = kv_sub_all = ws.get("kv_sub", n_sub, 2 * C, dtype, dev)
-            ops.layernorm(x, pr.ln1_w, pr.ln1_b, pr.eps, xn_sub, rowmap=rowmap, rows=n_sub)
-            if not defer_kv:
-                self._kv_gemm(pr, xn_sub, kv_sub, rope, dict(pos_rowmap=rowmap, **posctx))
-            if G > 1:
-                work_sub = gather_rows(kv_sub_all, kv_sub, [c * Pp for c in a_counts], group, r)
-            if cache_layer is not None:  # two-phase reloc: every anchor's subsample K|V of this layer
-                _wait(work_sub)
-                self._kv_cache_layers[cache_layer] = kv_sub_all.clone()
-        if G > 1:
-            # global block, first half: LN1 + Q GEMM locally, K/V straight into this rank's slot
-            xs = x[a0:q0]
-            xn, qkv = sc.xn[a0:q0], sc.qkv[a0:q0]
-            kv_all = ws.get("kv_all", La, 2 * C, dtype, dev)
-            kv_loc = ws.get("kv_loc", La_l, 2 * C, dtype, dev)
-            ops.layernorm(xs, pg.ln1_w, pg.ln1_b, pg.eps, xn)
-            epi = runtime.qkv_params(pg, rope, prescale=True, pos_row_base=a0, **posctx)
-            epi_kv = runtime.qkv_params(pg, rope, pos_row_base=a0, **posctx)
-            probs = []
-            if epi is not None and epi_kv is not None:
-                epi_kv["col_offset"] = C
-                probs = [dict(a=xn, w=pg.w_qkv[:C], out=qkv[:, :C], bias=_sl(pg.b_qkv, 0, C), qkv=epi),
-                         dict(a=xn, w=pg.w_qkv[C:], out=kv_loc, bias=_sl(pg.b_qkv, C, 3 * C), qkv=epi_kv)]
-            if probs and ops.gemm_group_eligible(probs):
-                # Q and K/V as ONE grouped launch: at G = 8 a rank's 5,496 anchor rows are 88 + 176
-                # tiles of 256^2, each under one workgroup round on its own
-                ops.gemm_group(probs, _lib.SR_EPI_QKV, tag="gemm")
-            else:
-                runtime.qkv_gemm(pg, xn, pg.w_qkv[:C], qkv[:, :C], _sl(pg.b_qkv, 0, C), epi, runtime.q_prescale(pg))
-                self._kv_gemm(pg, xn, kv_loc, rope, dict(pos_row_base=a0, **posctx))
-            work_kv = gather_rows(kv_all, kv_loc, [c * P for c in a_counts], group, r)
-        if paired:
-            # G == 1, bf16: the queries' and anchors' QKV projections (and the anchor-subsample K/V
-            # one) as ONE grouped GEMM launch, then the global block's attention (anchors against
-            # themselves) and the split reloc block's subsample pass (queries against the anchor
-            # subsample) in ONE launch of the hand-scheduled sweep (sr_attention_pair): each time the
-            # second problem fills the CUs the first one's last workgroup round leaves idle; then the
-            # reloc own-frame pass folds the subsample pass in, and both blocks' tails follow
-            rows, La = Nq_l * P, q0 - a0
-            n_full = n_sub_all // 64 * 64
-            epi_r = runtime.qkv_params(pr, rope, prescale=True, pos_row_base=q0, **posctx)
-            epi_g = runtime.qkv_params(pg, rope, prescale=True, pos_row_base=a0, **posctx)
-            epi_s = runtime.qkv_params(pr, rope, pos_rowmap=rowmap, **posctx) if defer_kv else None
-            if epi_s is not None:
-                epi_s["col_offset"] = C
-            probs = [dict(a=sc.xn[q0:q1], w=pr.w_qkv, out=sc.qkv[q0:q1], bias=pr.b_qkv, qkv=epi_r),
-                     dict(a=sc.xn[a0:q0], w=pg.w_qkv, out=sc.qkv[a0:q0], bias=pg.b_qkv, qkv=epi_g)]
-            if defer_kv:
-                probs.append(dict(a=xn_sub, w=pr.w_qkv[C:], out=kv_sub_all, bias=_sl(pr.b_qkv, C, 3 * C), qkv=epi_s))
-            if all(p_["qkv"] is not None for p_ in probs) and ops.gemm_group_eligible(probs):
-                ops.layernorm(x[q0:q1], pr.ln1_w, pr.ln1_b, pr.eps, sc.xn[q0:q1])
-                ops.layernorm(x[a0:q0], pg.ln1_w, pg.ln1_b, pg.eps, sc.xn[a0:q0])
-                ops.gemm_group(probs, _lib.SR_EPI_QKV, tag="gemm")
-            else:
-                runtime.run_block_head(pr, x, q0, q1, sc, epi_r, runtime.q_prescale(pr))
-                runtime.run_block_head(pg, x, a0, q0, sc, epi_g, runtime.q_prescale(pg))
-                if defer_kv:
-                    self._kv_gemm(pr, xn_sub, kv_sub_all, rope, dict(pos_rowmap=rowmap, **posctx))
-            qkv_r, qkv_g = sc.qkv[q0:q1], sc.qkv[a0:q0]
-            o_a, lse_a = ops.key_split_workspace(dev, 1, rows, C, pr.heads, name="reloc_split")
-            lse_a = lse_a[0]
-            pa = dict(q=qkv_g[:, 0:C], k0=qkv_g[:, C:2 * C], v0=qkv_g[:, 2 * C:3 * C], o=sc.o[a0:q0], lq=La, l0=La,
-                      key_norm_max=runtime.key_norm_bound(pg), query_norm_max=runtime.query_norm_bound(pg),
-                      q_scaled=_qs(pg))
-            pb = dict(q=qkv_r[:, 0:C], k0=kv_sub_all[:n_full, 0:C], v0=kv_sub_all[:n_full, C:2 * C], o=o_a, lq=rows,
-                      l0=n_full, key_norm_max=runtime.key_norm_bound(pr), query_norm_max=runtime.query_norm_bound(pr),
-                      lse=lse_a.view(-1), q_scaled=_qs(pr))
-            if ops.PAIR_VT:
-                # both problems' V as pre-transposed tiles: one ds_read_b128 per P.V fragment in the sweep
-                for p_, name, blk in ((pa, "vt_g", pg), (pb, "vt_s", pr)):
-                    p_["vt"] = ops.vt_tiles(p_["v0"], p_["l0"], blk.heads,
-                                            ws.get(name, *ops.vt_tile_shape(p_["l0"], blk.heads), dtype, dev),
-                                            tag="vt_tiles")
-            ops.attention_pair(pa, pb, heads=pg.heads, head_dim=pg.head_dim, tag="attn_global")
-            self._reloc_own_pass(pr, qkv_r, kv_sub_all, sc.o[q0:q1], o_a, lse_a, Nq_l, P, n_sub_all, n_full)
-            if runtime.group_tails_wanted(max(q1 - q0, q0 - a0)):
-                out.extend(runtime.run_block_tails([(pr, q0, q1), (pg, a0, q0)], x, sc, defer=defer))
-            else:
-                keep(runtime.run_block_tail(pr, x, q0, q1, sc, defer=defer))
-                keep(runtime.run_block_tail(pg, x, a0, q0, sc, defer=defer))
-            return out
-        # G == 1: the reloc block (query rows) and the global block (anchor rows) are independent.
-        # SR_CONCURRENT_STACKS=1 runs the reloc block on a side stream so that each could fill the
-        # other's last partial wave.  Round 1: 3% SLOWER at N=32 (68.7 -> 66.7 views/s).  Round 3,
-        # with the one-workgroup-per-CU asm attention and the split reloc: 0.8 % faster (409.4 / 409.1
-        # vs 411.9 / 413.2 ms, one box, interleaved; C2 / C3 goldens pass), but the kernels of the two
-        # streams then overlap, so no per-kernel time (HIP events or rocprofv3) measures a kernel any
-        # more -- the roofline of the dominant kernel reads 0.40 instead of 0.50.  Off by default,
-        # so that the bench's roofline stays a measurement of the kernel.
-        side = self._side_stream(dev) if (G == 1 and Nq_l > 0 and a0 < q0) else None
-        # frame-sharded: the reloc block's tail waits for the global attention and runs grouped with
-        # the global block's (runtime.run_block_tails: one launch per GEMM stage over both row ranges)
-        group_tails = G > 1 and Nq_l > 0 and runtime.group_tails_wanted(max(q1 - q0, q0 - a0))
-        # ... and with SR_SHARD_CONCURRENT=1 its attention runs on a second stream beside the global
-        # attention's key-split passes: at G = 8 both under-fill the chip on their own
-        shard_side = (self._stream2(dev) if group_tails and _SHARD_CONCURRENT and torch.device(dev).type == "cuda"
-                      else None)
-        if Nq_l > 0:
-            def attend_reloc(qkv, o):
-                _wait(work_sub)
-                rows = Nq_l * P
-                kb, qb = runtime.key_norm_bound(pr), runtime.query_norm_bound(pr)
-                if self._split_reloc(dtype, rows, n_sub_all):
-                    # two passes merged by their LSEs (the union of the two key sets, exactly): every
-                    # query row against the shared anchor subsample's whole 64-key tiles as ONE long
-                    # query set (the hand-scheduled sweep, sr_attn.hip), then each query frame against
-                    # the subsample's last partial tile (shared segment 0) and itself (segment 1) on
-                    # the compiled sweep, whose epilogue folds the first pass in (sr_attn_desc.merge_o)
-                    n_full = n_sub_all // 64 * 64
-                    o_a, lse_a = ops.key_split_workspace(dev, 1, rows, C, pr.heads, name="reloc_split")
-                    lse_a = lse_a[0]
-                    ops.attention(qkv[:, 0:C], kv_sub_all[:n_full, 0:C], kv_sub_all[:n_full, C:2 * C],
-                                  o_a, heads=pr.heads, head_dim=pr.head_dim, batch=1, lq=rows,
-                                  q_bstride=0, l0=n_full, k0_bstride=0, tag="attn_reloc", key_norm_max=kb,
-                                  query_norm_max=qb,
-                                  lse=lse_a.view(-1), tail_readable=True, q_scaled=_qs(pr))
-                    self._reloc_own_pass(pr, qkv, kv_sub_all, o, o_a, lse_a, Nq_l, P, n_sub_all, n_full)
-                    return
-                ops.attention(qkv[:, 0:C], kv_sub_all[:, 0:C], kv_sub_all[:, C:2 * C], o, heads=pr.heads,
-                              head_dim=pr.head_dim, batch=Nq_l, lq=P, q_bstride=P, l0=n_sub_all, k0_bstride=0,
-                              k1=qkv[:, C:2 * C], v1=qkv[:, 2 * C:3 * C], l1=P, k1_bstride=P, tag="attn_reloc",
-                              key_norm_max=kb, query_norm_max=qb, tail_readable=True, q_scaled=_qs(pr))
-            if side is not None:
-                side.wait_stream(torch.cuda.current_stream(dev))  # frame block + subsample K/V are done
-                with torch.cuda.stream(side):
-                    runtime.run_block(pr, x, q0, q1, sc, attend_reloc,
-                                      runtime.qkv_params(pr, rope, prescale=True, pos_row_base=q0, **posctx),
-                                      q_scale=runtime.q_prescale(pr))
-            elif group_tails:  # the tail joins the global block's in run_block_tails below
-                runtime.run_block_head(pr, x, q0, q1, sc,
-                                       runtime.qkv_params(pr, rope, prescale=True, pos_row_base=q0, **posctx),
-                                       runtime.q_prescale(pr))
-                if shard_side is not None:
-                    shard_side.wait_stream(torch.cuda.current_stream(dev))  # the reloc QKV is done
-                    with torch.cuda.stream(shard_side):  # (its wait on the subsample gather too)
-                        attend_reloc(sc.qkv[q0:q1], sc.o[q0:q1])
-                else:
-                    attend_reloc(sc.qkv[q0:q1], sc.o[q0:q1])
-            else:
-                keep(runtime.run_block(pr, x, q0, q1, sc, attend_reloc,
-                                       runtime.qkv_params(pr, rope, prescale=True, pos_row_base=q0, **posctx),
-                                       defer=defer, q_scale=runtime.q_prescale(pr)))
-        _wait(work_sub)  # a rank without query frames still fed the others (send buffer reuse)
-        if G > 1:
-            o, q = sc.o[a0:q0], sc.qkv[a0:q0, 0:C]
-            fp8 = self.fp8_global and pg.head_dim == 64 and q.dtype == torch.bfloat16
-            if self.shard_overlap and not fp8:
-                self._global_attention_sharded(q, kv_loc, kv_all, o, pg, La_l, La, sum(a_counts[:r]) * P, work_kv)
-            else:
-                _wait(work_kv)
-                self._global_attention(q, kv_all[:, 0:C], kv_all[:, C:2 * C], o, pg, La_l, La)
-            if shard_side is not None:
-                torch.cuda.current_stream(dev).wait_stream(shard_side)  # join before the grouped tails
-            if group_tails:
-                out.extend(runtime.run_block_tails([(pr, q0, q1), (pg, a0, q0)], x, sc, defer=defer))
-            else:
-                keep(runtime.run_block_tail(pg, x, a0, q0, sc, defer=defer))
+    def _kv_epi(self, ctx: _LayerCtx, pb, **pos) -> Optional[dict]:
+        """Epilogue of a K/V-only projection (runtime.kv_gemm); ``pos``: pos_rowmap= or pos_row_base=."""
+        return runtime.kv_params(pb, ctx.rope, **pos, **ctx.posctx)
+
+    def _frame_block(self, ctx: _LayerCtx, l: int, frames: int, pending: Optional[list] = None) -> None:
+        """Frame block l over every row of x (``pending``: residual updates its LN1 folds in)."""
+        pb = self.frame_blocks[l].packed(ctx.dtype)
+        runtime.run_block(pb, ctx.x, 0, frames * ctx.P, ctx.sc,
+                          runtime.frame_attend(pb, frames, ctx.P, tail_readable=True, q_scaled=_qs(pb)),
+                          self._epi(ctx, pb, 0), pending=pending, q_scale=runtime.q_prescale(pb))
+
+    def _copy_query_half(self, ctx: _LayerCtx, out_map: torch.Tensor, half: int) -> None:
+        """x's query rows -> the frame (0) or reloc (1) half of an intermediate map [B, Nq_l, P, 2C]."""
+        C = self.embed_dim
+        for b in range(out_map.shape[0]):
+            _, q0, q1 = ctx.rows(b)
+            ops.copy_rows(out_map[b].view(q1 - q0, 2 * C)[:, half * C:(half + 1) * C], ctx.x[q0:q1], q1 - q0)
+
+    def _layer_global(self, ctx: _LayerCtx, b: int) -> list:
+        """global_reloc (queries, aggregator.py:672-741) + global (anchors, :743-769) blocks of one layer
+        for one batch item, by one of three executors (each returns what run_block / run_block_tail(s)
+        gave it).  Returns the fc2 residuals left pending for the next LN1 (ctx.defer; else [])."""
+        a0, q0, q1 = ctx.rows(b)
+        paired = ctx.G == 1 and self._paired_attention(ctx.pr, ctx.pg, ctx.dtype, q1 - q0, q0 - a0, ctx.Na_l * ctx.Pp)
+        run = self._layer_sharded if ctx.G > 1 else self._layer_paired if paired else self._layer_plain
+        return [p for p in run(ctx, b) if p is not None]
+
+    def _subsample_kv(self, ctx: _LayerCtx, b: int, project: bool = True):
+        """Anchor-subsample K/V (reads x before the global block updates the anchors): row-mapped LN1, the
+        projection unless the caller groups it, the gather, the cache's copy -> (xn_sub, kv_sub_all, works)."""
+        pr, ws, C, G = ctx.pr, self._ws, ctx.pr.dim, ctx.G
+        n_sub = ctx.Na_l * ctx.Pp                  # local anchor-subsample rows
+        xn_sub = ws.get("xn_sub", n_sub, C, ctx.dtype, ctx.dev)
+        if G > 1:  # separate send buffer: no aliasing between collective input and output
+            kv_sub = ws.get("kv_sub_loc", n_sub, 2 * C, ctx.dtype, ctx.dev)
+            kv_sub_all = ws.get("kv_sub", sum(ctx.a_counts) * ctx.Pp, 2 * C, ctx.dtype, ctx.dev)
         else:
-            def attend_global(qkv, o):
-                self._global_attention(qkv[:, 0:C], qkv[:, C:2 * C], qkv[:, 2 * C:3 * C], o, pg, La, La)
-            keep(runtime.run_block(pg, x, a0, q0, sc, attend_global,
-                                   runtime.qkv_params(pg, rope, prescale=True, pos_row_base=a0, **posctx),
-                                   defer=defer, q_scale=runtime.q_prescale(pg)))
-        if side is not None:
-            torch.cuda.current_stream(dev).wait_stream(side)  # join before the next frame block
-        return out
+            kv_sub = kv_sub_all = ws.get("kv_sub", n_sub, 2 * C, ctx.dtype, ctx.dev)
+        rowmap = ctx.rowmap_t[ctx.l, b]
+        ops.layernorm(ctx.x, pr.ln1_w, pr.ln1_b, pr.eps, xn_sub, rowmap=rowmap, rows=n_sub)
+        if project:
+            runtime.kv_gemm(pr, xn_sub, kv_sub, self._kv_epi(ctx, pr, pos_rowmap=rowmap))
+        work = gather_rows(kv_sub_all, kv_sub, [c * ctx.Pp for c in ctx.a_counts], ctx.group, ctx.r) if G > 1 else []
+        if ctx.fill_cache:  # two-phase reloc: every anchor's subsample K|V of this layer
+            _wait(work)
+            self._kv_cache_layers[ctx.l] = kv_sub_all.clone()
+        return xn_sub, kv_sub_all, work
 
-    def _layer_global_camera(self, pr, pg, x, sc, rowmap, Pp, a0, q0, q1, Na, Nq, P, rope, posctx, dtype, dev,
-                             anchor_rows, query_rows, cam_a, cam_q) -> None:
-        """The LAST layer's global_reloc + global blocks of one batch item when only the camera rows
-        are read (forward(outputs="camera"), G == 1): LN1 and the QKV projection run for every row as
-        in _layer_global (every row is a key), then only row 0 of each frame goes on --
-          * attention: the anchors' camera rows as one query set against every anchor token
-            (global); the queries' camera rows as one query set against the shared anchor subsample
-            and each against its own frame (batch = Nq, lq = 1), merged by their LSEs (reloc):
-            ops.attention_rows, sets of at most 64 rows;
-          * proj + LayerScale residual, LN2, fc1 + GELU, fc2 + LayerScale residual on a compact
-            [Na + Nq, C] fp32 stream gathered from x (runtime.run_block_tails: one grouped launch
-            per stage for the two blocks where eligible).
-        The results land in ``cam_a`` / ``cam_q`` ([Na, C] / [Nq, C] views); x is not updated.
-        fp32 compute runs the same plumbing on the exact sr_attention kernel."""
-        C, ws, H, D = pg.dim, self._ws, pg.heads, pg.head_dim
-        n_sub = Na * Pp
-        xn_sub = ws.get("xn_sub", n_sub, C, dtype, dev)
-        kv_sub = ws.get("kv_sub", n_sub, 2 * C, dtype, dev)
-        ops.layernorm(x, pr.ln1_w, pr.ln1_b, pr.eps, xn_sub, rowmap=rowmap, rows=n_sub)
-        epi_r = runtime.qkv_params(pr, rope, prescale=True, pos_row_base=q0, **posctx)
-        epi_g = runtime.qkv_params(pg, rope, prescale=True, pos_row_base=a0, **posctx)
-        epi_s = runtime.qkv_params(pr, rope, pos_rowmap=rowmap, **posctx)
-        if epi_s is not None:
-            epi_s["col_offset"] = C
+    def _project_heads(self, ctx: _LayerCtx, b: int) -> torch.Tensor:
+        """LN1 + QKV projection of the reloc (query rows) and global (anchor rows) blocks and the subsample
+        K/V projection: ONE grouped GEMM launch where all are eligible, else block by block -> kv_sub."""
+        pr, pg, x, sc, C = ctx.pr, ctx.pg, ctx.x, ctx.sc, ctx.pg.dim
+        a0, q0, q1 = ctx.rows(b)
+        xn_sub, kv_sub, _ = self._subsample_kv(ctx, b, project=False)
+        epi_r, epi_g = self._epi(ctx, pr, q0), self._epi(ctx, pg, a0)
+        epi_s = self._kv_epi(ctx, pr, pos_rowmap=ctx.rowmap_t[ctx.l, b])
         probs = [dict(a=sc.xn[q0:q1], w=pr.w_qkv, out=sc.qkv[q0:q1], bias=pr.b_qkv, qkv=epi_r),
                  dict(a=sc.xn[a0:q0], w=pg.w_qkv, out=sc.qkv[a0:q0], bias=pg.b_qkv, qkv=epi_g),
                  dict(a=xn_sub, w=pr.w_qkv[C:], out=kv_sub, bias=_sl(pr.b_qkv, C, 3 * C), qkv=epi_s)]
@@ -804,16 +647,204 @@ class Aggregator(nn.Module):
         else:
             runtime.run_block_head(pr, x, q0, q1, sc, epi_r, runtime.q_prescale(pr))
             runtime.run_block_head(pg, x, a0, q0, sc, epi_g, runtime.q_prescale(pg))
-            self._kv_gemm(pr, xn_sub, kv_sub, rope, dict(pos_rowmap=rowmap, **posctx))
+            runtime.kv_gemm(pr, xn_sub, kv_sub, epi_s)
+        return kv_sub
+
+    def _reloc_attention(self, ctx: _LayerCtx, kv_sub_all, work_sub: list, qkv, o, pair: Optional[dict] = None) -> None:
+        """The reloc block's attention (run_block's ``attend``; ``work_sub``: the subsample's gather): one
+        launch, or (_split_reloc) two passes merged by their LSEs (the union of the two key sets, exactly):
+        every query row against the shared anchor subsample's whole 64-key tiles as ONE long query set (the
+        hand-scheduled sweep, sr_attn.hip; in ops.attention_pair's launch behind ``pair``, the global
+        attention), then each query frame against the subsample's last partial tile (shared segment 0) and
+        itself (segment 1) on the compiled sweep, whose epilogue folds the first pass in (sr_attn_desc.merge_o)."""
+        _wait(work_sub)
+        pr, pg, C, rows, n_sub_all = ctx.pr, ctx.pg, ctx.pr.dim, qkv.shape[0], kv_sub_all.shape[0]
+        if not self._split_reloc(ctx.dtype, rows, n_sub_all):
+            self._reloc_one_launch(ctx, kv_sub_all, qkv, o, tail_readable=True)
+            return
+        n_full = n_sub_all // 64 * 64
+        kb, qb = runtime.key_norm_bound(pr), runtime.query_norm_bound(pr)
+        o_a, lse_a = ops.key_split_workspace(ctx.dev, 1, rows, C, pr.heads, name="reloc_split")
+        lse_a = lse_a[0]
+        sub = dict(lq=rows, l0=n_full, key_norm_max=kb, query_norm_max=qb, lse=lse_a.view(-1), q_scaled=_qs(pr))
+        q, k0, v0 = qkv[:, 0:C], kv_sub_all[:n_full, 0:C], kv_sub_all[:n_full, C:2 * C]
+        if pair is None:
+            ops.attention(q, k0, v0, o_a, heads=pr.heads, head_dim=pr.head_dim, batch=1, q_bstride=0, k0_bstride=0,
+                          tag="attn_reloc", tail_readable=True, **sub)
+        else:
+            sub.update(q=q, k0=k0, v0=v0, o=o_a)
+            if ops.PAIR_VT:
+                # both problems' V as pre-transposed tiles: one ds_read_b128 per P.V fragment in the sweep
+                for p_, name, blk in ((pair, "vt_g", pg), (sub, "vt_s", pr)):
+                    p_["vt"] = ops.vt_tiles(p_["v0"], p_["l0"], blk.heads, self._ws.get(
+                        name, *ops.vt_tile_shape(p_["l0"], blk.heads), ctx.dtype, ctx.dev), tag="vt_tiles")
+            ops.attention_pair(pair, sub, heads=pg.heads, head_dim=pg.head_dim, tag="attn_global")
+        if n_full < n_sub_all:
+            self._reloc_one_launch(ctx, kv_sub_all[n_full:], qkv, o, tail_readable=True, merge_o=o_a, merge_lse=lse_a)
+        else:
+            ops.attention(q, qkv[:, C:2 * C], qkv[:, 2 * C:3 * C], o, heads=pr.heads, head_dim=pr.head_dim,
+                          batch=ctx.Nq_l, lq=ctx.P, q_bstride=ctx.P, l0=ctx.P, k0_bstride=ctx.P, tag="attn_reloc",
+                          key_norm_max=kb, query_norm_max=qb, tail_readable=True, merge_o=o_a, merge_lse=lse_a,
+                          q_scaled=_qs(pr))
+
+    def _reloc_one_launch(self, ctx: _LayerCtx, kv, qkv, o, **more) -> None:
+        """Each query frame against the shared subsample K|V rows ``kv`` and itself.  ``more``: tail_readable=True
+        where ``kv`` is in a padded Workspace buffer (a kv-cache clone is not), merge_o= / merge_lse= to fold in."""
+        pr, C, P = ctx.pr, ctx.pr.dim, ctx.P
+        ops.attention(qkv[:, 0:C], kv[:, 0:C], kv[:, C:2 * C], o, heads=pr.heads, head_dim=pr.head_dim,
+                      batch=ctx.Nq_l, lq=P, q_bstride=P, l0=kv.shape[0], k0_bstride=0, k1=qkv[:, C:2 * C],
+                      v1=qkv[:, 2 * C:3 * C], l1=P, k1_bstride=P, tag="attn_reloc",
+                      key_norm_max=runtime.key_norm_bound(pr), query_norm_max=runtime.query_norm_bound(pr),
+                      q_scaled=_qs(pr), **more)
+
+    def _layer_paired(self, ctx: _LayerCtx, b: int) -> list:
+        """G == 1, bf16 (_paired_attention): the queries' and anchors' QKV projections and the
+        anchor-subsample K/V one as ONE grouped GEMM launch (the subsample's LayerNorm still reads x
+        first, before the global block updates it), then the global block's attention (anchors against
+        themselves) and the split reloc block's subsample pass (queries against the anchor
+        subsample) in ONE launch of the hand-scheduled sweep (sr_attention_pair): each time the
+        second problem fills the CUs the first one's last workgroup round leaves idle; then the
+        reloc own-frame pass folds the subsample pass in, and both blocks' tails follow.  (Pairing
+        needs query rows: the subsample is wanted and no cache is being filled.)"""
+        pr, pg, x, sc, C = ctx.pr, ctx.pg, ctx.x, ctx.sc, ctx.pg.dim
+        a0, q0, q1 = ctx.rows(b)
+        La = q0 - a0  # anchor tokens
+        kv_sub = self._project_heads(ctx, b)
         qkv_r, qkv_g = sc.qkv[q0:q1], sc.qkv[a0:q0]
-        n = Na + Nq
-        hid = pg.w_fc1.shape[0]
+        pa = dict(q=qkv_g[:, 0:C], k0=qkv_g[:, C:2 * C], v0=qkv_g[:, 2 * C:3 * C], o=sc.o[a0:q0], lq=La, l0=La,
+                  key_norm_max=runtime.key_norm_bound(pg), query_norm_max=runtime.query_norm_bound(pg),
+                  q_scaled=_qs(pg))
+        self._reloc_attention(ctx, kv_sub, [], qkv_r, sc.o[q0:q1], pair=pa)
+        items = [(pr, q0, q1), (pg, a0, q0)]
+        if runtime.group_tails_wanted(max(q1 - q0, La)):
+            return runtime.run_block_tails(items, x, sc, defer=ctx.defer)
+        return [runtime.run_block_tail(blk, x, r0, r1, sc, defer=ctx.defer) for blk, r0, r1 in items]
+
+    def _layer_plain(self, ctx: _LayerCtx, b: int) -> list:
+        """G == 1, unpaired: the reloc block (query rows) and the global block (anchor rows), one
+        after the other through runtime.run_block; they are independent.
+        SR_CONCURRENT_STACKS=1 runs the reloc block on a side stream so that each could fill the
+        other's last partial wave.  Round 1: 3% SLOWER at N=32 (68.7 -> 66.7 views/s).  Round 3,
+        with the one-workgroup-per-CU asm attention and the split reloc: 0.8 % faster (409.4 / 409.1
+        vs 411.9 / 413.2 ms, one box, interleaved; C2 / C3 goldens pass), but the kernels of the two
+        streams then overlap, so no per-kernel time (HIP events or rocprofv3) measures a kernel any
+        more -- the roofline of the dominant kernel reads 0.40 instead of 0.50.  Off by default,
+        so that the bench's roofline stays a measurement of the kernel."""
+        pr, pg, x, sc, dev, C = ctx.pr, ctx.pg, ctx.x, ctx.sc, ctx.dev, ctx.pg.dim
+        a0, q0, q1 = ctx.rows(b)
+        La = q0 - a0                   # anchor tokens
+        out = []
+        kv_sub = self._subsample_kv(ctx, b)[1] if ctx.rowmap_t is not None else None
+        side = self._aux_stream("_side", dev) if (_concurrent_stacks() and ctx.Nq_l > 0 and a0 < q0) else None
+        if ctx.Nq_l > 0:
+            attend_reloc = partial(self._reloc_attention, ctx, kv_sub, [])
+            if side is not None:
+                side.wait_stream(torch.cuda.current_stream(dev))  # frame block + subsample K/V are done
+                with torch.cuda.stream(side):
+                    runtime.run_block(pr, x, q0, q1, sc, attend_reloc, self._epi(ctx, pr, q0),
+                                      q_scale=runtime.q_prescale(pr))
+            else:
+                out.append(runtime.run_block(pr, x, q0, q1, sc, attend_reloc, self._epi(ctx, pr, q0),
+                                             defer=ctx.defer, q_scale=runtime.q_prescale(pr)))
+
+        def attend_global(qkv, o):
+            self._global_attention(qkv[:, 0:C], qkv[:, C:2 * C], qkv[:, 2 * C:3 * C], o, pg, La, La)
+        out.append(runtime.run_block(pg, x, a0, q0, sc, attend_global, self._epi(ctx, pg, a0), defer=ctx.defer,
+                                     q_scale=runtime.q_prescale(pg)))
+        if side is not None:
+            torch.cuda.current_stream(dev).wait_stream(side)  # join before the next frame block
+        return out
+
+    def _layer_sharded(self, ctx: _LayerCtx, b: int) -> list:
+        """G > 1: the anchor K/V and the anchor-subsample K/V are gathered asynchronously
+        (``gather_rows``; ``ctx.a_counts`` = anchor frames per rank): the subsample K/V behind the
+        query-side QKV GEMM, the anchor K/V behind the whole reloc block and the local-anchor
+        attention pass."""
+        pr, pg, x, sc, dev, C = ctx.pr, ctx.pg, ctx.x, ctx.sc, ctx.dev, ctx.pg.dim
+        a0, q0, q1 = ctx.rows(b)
+        La_l = q0 - a0                     # local anchor tokens
+        La = sum(ctx.a_counts) * ctx.P     # all anchor tokens
+        out = []
+        kv_sub_all, work_sub = self._subsample_kv(ctx, b)[1:] if ctx.rowmap_t is not None else (None, [])
+        # global block, first half: LN1 + Q GEMM locally, K/V straight into this rank's slot
+        xn, qkv = sc.xn[a0:q0], sc.qkv[a0:q0]
+        kv_all = self._ws.get("kv_all", La, 2 * C, ctx.dtype, dev)
+        kv_loc = self._ws.get("kv_loc", La_l, 2 * C, ctx.dtype, dev)
+        ops.layernorm(x[a0:q0], pg.ln1_w, pg.ln1_b, pg.eps, xn)
+        epi, epi_kv = self._epi(ctx, pg, a0), self._kv_epi(ctx, pg, pos_row_base=a0)
+        probs = []
+        if epi is not None and epi_kv is not None:
+            probs = [dict(a=xn, w=pg.w_qkv[:C], out=qkv[:, :C], bias=_sl(pg.b_qkv, 0, C), qkv=epi),
+                     dict(a=xn, w=pg.w_qkv[C:], out=kv_loc, bias=_sl(pg.b_qkv, C, 3 * C), qkv=epi_kv)]
+        if probs and ops.gemm_group_eligible(probs):
+            # Q and K/V as ONE grouped launch: at G = 8 a rank's 5,496 anchor rows are 88 + 176
+            # tiles of 256^2, each under one workgroup round on its own
+            ops.gemm_group(probs, _lib.SR_EPI_QKV, tag="gemm")
+        else:
+            runtime.qkv_gemm(pg, xn, pg.w_qkv[:C], qkv[:, :C], _sl(pg.b_qkv, 0, C), epi, runtime.q_prescale(pg))
+            runtime.kv_gemm(pg, xn, kv_loc, epi_kv)
+        work_kv = gather_rows(kv_all, kv_loc, [c * ctx.P for c in ctx.a_counts], ctx.group, ctx.r)
+        # the reloc block's tail waits for the global attention and runs grouped with the global
+        # block's (runtime.run_block_tails: one launch per GEMM stage over both row ranges)
+        group_tails = ctx.Nq_l > 0 and runtime.group_tails_wanted(max(q1 - q0, q0 - a0))
+        # ... and with SR_SHARD_CONCURRENT=1 its attention runs on a second stream beside the global
+        # attention's key-split passes: at G = 8 both under-fill the chip on their own
+        shard_side = (self._aux_stream("_shard_side", dev)
+                      if group_tails and _SHARD_CONCURRENT and torch.device(dev).type == "cuda" else None)
+        if ctx.Nq_l > 0:
+            attend_reloc = partial(self._reloc_attention, ctx, kv_sub_all, work_sub)
+            if group_tails:  # the tail joins the global block's in run_block_tails below
+                runtime.run_block_head(pr, x, q0, q1, sc, self._epi(ctx, pr, q0), runtime.q_prescale(pr))
+                if shard_side is not None:
+                    shard_side.wait_stream(torch.cuda.current_stream(dev))  # the reloc QKV is done
+                    with torch.cuda.stream(shard_side):  # (its wait on the subsample gather too)
+                        attend_reloc(sc.qkv[q0:q1], sc.o[q0:q1])
+                else:
+                    attend_reloc(sc.qkv[q0:q1], sc.o[q0:q1])
+            else:
+                out.append(runtime.run_block(pr, x, q0, q1, sc, attend_reloc, self._epi(ctx, pr, q0),
+                                             defer=ctx.defer, q_scale=runtime.q_prescale(pr)))
+        _wait(work_sub)  # a rank without query frames still fed the others (send buffer reuse)
+        o, q = sc.o[a0:q0], sc.qkv[a0:q0, 0:C]
+        fp8 = self.fp8_global and pg.head_dim == 64 and q.dtype == torch.bfloat16
+        if self.shard_overlap and not fp8:
+            self._global_attention_sharded(q, kv_loc, kv_all, o, pg, La_l, La, sum(ctx.a_counts[:ctx.r]) * ctx.P,
+                                           work_kv)
+        else:
+            _wait(work_kv)
+            self._global_attention(q, kv_all[:, 0:C], kv_all[:, C:2 * C], o, pg, La_l, La)
+        if shard_side is not None:
+            torch.cuda.current_stream(dev).wait_stream(shard_side)  # join before the grouped tails
+        if group_tails:
+            return out + runtime.run_block_tails([(pr, q0, q1), (pg, a0, q0)], x, sc, defer=ctx.defer)
+        return out + [runtime.run_block_tail(pg, x, a0, q0, sc, defer=ctx.defer)]
+
+    def _layer_global_camera(self, ctx: _LayerCtx, b: int, anchor_rows, query_rows, cam_a, cam_q) -> None:
+        """The LAST layer's global_reloc + global blocks of one batch item when only the camera rows
+        are read (forward(outputs="camera"), G == 1): LN1 and the QKV projection run for every row as
+        in _layer_paired (every row is a key), then only row 0 of each frame goes on --
+          * attention: the anchors' camera rows as one query set against every anchor token
+            (global); the queries' camera rows as one query set against the shared anchor subsample
+            and each against its own frame (batch = Nq, lq = 1), merged by their LSEs (reloc):
+            ops.attention_rows, sets of at most 64 rows;
+          * proj + LayerScale residual, LN2, fc1 + GELU, fc2 + LayerScale residual on a compact
+            [Na + Nq, C] fp32 stream gathered from x (runtime.run_block_tails: one grouped launch
+            per stage for the two blocks where eligible).
+        The results land in item b's rows of ``cam_a`` / ``cam_q`` ([B * Na, 2C] / [B * Nq, 2C]; reloc
+        half), ``anchor_rows`` / ``query_rows`` being the camera rows of x; x is not updated.
+        fp32 compute runs the same plumbing on the exact sr_attention kernel."""
+        pr, pg, x, sc, ws, dtype, dev = ctx.pr, ctx.pg, ctx.x, ctx.sc, self._ws, ctx.dtype, ctx.dev
+        C, H, D, P, Na, Nq = pg.dim, pg.heads, pg.head_dim, ctx.P, ctx.Na_l, ctx.Nq_l
+        a0, q0, q1 = ctx.rows(b)
+        kv_sub = self._project_heads(ctx, b)
+        qkv_r, qkv_g = sc.qkv[q0:q1], sc.qkv[a0:q0]
+        n, n_sub, hid = Na + Nq, kv_sub.shape[0], pg.w_fc1.shape[0]
         # compact scratch: rows [0, Na) the anchors' camera rows, [Na, n) the queries'
         cs = runtime.BlockScratch(xn=ws.get("cam_xn", n, C, dtype, dev), qkv=ws.get("cam_y", n, C, dtype, dev),
                                   o=ws.get("cam_o", n, C, dtype, dev), h=ws.get("cam_h", n, hid, dtype, dev))
         xc = ws.get("cam_x", n, C, torch.float32, dev)
-        ops.copy_rows(xc[:Na], x, Na, rowmap=anchor_rows)
-        ops.copy_rows(xc[Na:], x, Nq, rowmap=query_rows)
+        ops.copy_rows(xc[:Na], x, Na, rowmap=anchor_rows[b * Na:(b + 1) * Na])
+        ops.copy_rows(xc[Na:], x, Nq, rowmap=query_rows[b * Nq:(b + 1) * Nq])
         # row 0 of every frame, read in place from the packed q|k|v rows (row stride P * 3C)
         q_g = qkv_g.view(Na, P * 3 * C)[:, 0:C]
         q_r = qkv_r.view(Nq, P * 3 * C)[:, 0:C]
@@ -834,8 +865,8 @@ class Aggregator(nn.Module):
             ops.attn_merge_n(o_parts, lse_parts, cs.o[Na + s0:Na + s0 + m], parts=2, rows=m, heads=H, head_dim=D,
                              seg_rows=[m, 1])
         runtime.run_block_tails([(pr, Na, n), (pg, 0, Na)], xc, cs, defer=False)
-        ops.copy_rows(cam_a, xc[:Na], Na)
-        ops.copy_rows(cam_q, xc[Na:], Nq)
+        ops.copy_rows(cam_a[b * Na:(b + 1) * Na, C:], xc[:Na], Na)
+        ops.copy_rows(cam_q[b * Nq:(b + 1) * Nq, C:], xc[Na:], Nq)
 
     def set_fp8_global(self, enabled: bool = True, fp8_v: bool = False):
         """Global blocks' q.k^T in block-scaled fp8 (BASELINE C5); with ``fp8_v`` also V and P.V.
@@ -907,31 +938,13 @@ class Aggregator(nn.Module):
                           k0_bstride=0, tag="attn_global", key_norm_max=runtime.key_norm_bound(pg),
                           query_norm_max=runtime.query_norm_bound(pg), q_scaled=_qs(pg))
 
-    @staticmethod
-    def _reloc_own_pass(pr, qkv, kv_sub_all, o, o_a, lse_a, nq: int, P: int, n_sub_all: int, n_full: int) -> None:
-        """Second pass of the split reloc attention: each query frame against the subsample's last
-        partial tile (shared segment 0) and itself (segment 1), folding the subsample pass's
-        (o_a, lse_a) in at its epilogue (sr_attn_desc.merge_o) -> o."""
-        C, kb, qb = pr.dim, runtime.key_norm_bound(pr), runtime.query_norm_bound(pr)
-        if n_full < n_sub_all:
-            ops.attention(qkv[:, 0:C], kv_sub_all[n_full:, 0:C], kv_sub_all[n_full:, C:2 * C], o, heads=pr.heads,
-                          head_dim=pr.head_dim, batch=nq, lq=P, q_bstride=P, l0=n_sub_all - n_full, k0_bstride=0,
-                          k1=qkv[:, C:2 * C], v1=qkv[:, 2 * C:3 * C], l1=P, k1_bstride=P, tag="attn_reloc",
-                          key_norm_max=kb, query_norm_max=qb, tail_readable=True, merge_o=o_a, merge_lse=lse_a,
-                          q_scaled=_qs(pr))
-        else:
-            ops.attention(qkv[:, 0:C], qkv[:, C:2 * C], qkv[:, 2 * C:3 * C], o, heads=pr.heads, head_dim=pr.head_dim,
-                          batch=nq, lq=P, q_bstride=P, l0=P, k0_bstride=P, tag="attn_reloc", key_norm_max=kb,
-                          query_norm_max=qb,
-                          tail_readable=True, merge_o=o_a, merge_lse=lse_a, q_scaled=_qs(pr))
-
     def _paired_attention(self, pr, pg, dtype, rows: int, La: int, n_sub: int) -> bool:
         """Single GPU, bf16, split reloc, a global query set that fills the chip without key
         splitting: the global attention and the reloc subsample pass in one launch
         (ops.attention_pair; SR_ATTN_PAIR=0 launches them apart)."""
         if not self._split_reloc(dtype, rows, n_sub) or self.fp8_global or La <= 0 or pg.heads != pr.heads:
             return False
-        if os.environ.get("SR_CONCURRENT_STACKS", "0") == "1":
+        if _concurrent_stacks():
             return False
         if ops.key_split_parts(dtype=dtype, batch=1, lq=La, heads=pg.heads, l0=La, l1=0, mask_mode=0) != 1:
             return False
@@ -949,33 +962,14 @@ class Aggregator(nn.Module):
         return (os.environ.get("SR_RELOC_SPLIT", "1") == "1" and dtype == torch.bfloat16 and
                 (rows + 255) // 256 * 16 >= _RELOC_SPLIT_MIN_WG and n_sub >= 64)
 
-    def _stream2(self, dev):
-        """Second HIP stream of the frame-sharded reloc attention (SR_SHARD_CONCURRENT=1)."""
-        s = getattr(self, "_shard_side", None)
+    def _aux_stream(self, attr: str, dev):
+        """The second HIP stream kept in ``attr``: ``_shard_side`` for the frame-sharded reloc attention
+        (SR_SHARD_CONCURRENT=1), ``_side`` for the concurrent reloc block (opt-in: SR_CONCURRENT_STACKS=1)."""
+        s = getattr(self, attr, None)
         if s is None or s.device != torch.device(dev):
             s = torch.cuda.Stream(device=dev)
-            self._shard_side = s
+            setattr(self, attr, s)
         return s
-
-    def _side_stream(self, dev):
-        """Second HIP stream for the concurrent reloc block (opt-in: SR_CONCURRENT_STACKS=1)."""
-        if os.environ.get("SR_CONCURRENT_STACKS", "0") != "1":
-            return None
-        s = getattr(self, "_side", None)
-        if s is None or s.device != torch.device(dev):
-            s = torch.cuda.Stream(device=dev)
-            self._side = s
-        return s
-
-    def _kv_gemm(self, pb, xn, out, rope, pos):
-        """K/V-only projection (qkv weight rows C..3C) with k-norm + RoPE on the K half."""
-        C = pb.dim
-        epi = runtime.qkv_params(pb, rope, **pos)
-        if epi is None:
-            ops.gemm(xn, pb.w_qkv[C:], out, _lib.SR_EPI_BIAS, bias=_sl(pb.b_qkv, C, 3 * C), tag="gemm")
-        else:
-            epi["col_offset"] = C
-            ops.gemm(xn, pb.w_qkv[C:], out, _lib.SR_EPI_QKV, bias=_sl(pb.b_qkv, C, 3 * C), qkv=epi, tag="gemm")
 
 
 # SR_SHARD_TAIL=1 (opt-in): the frame-sharded global block's key-split passes declare their chunk
@@ -1003,6 +997,11 @@ def _sl(t, a, b):
 def _qs(pb) -> bool:
     """Whether pb's QKV GEMMs here write c*q (runtime.q_prescale): the attention takes q_scaled."""
     return runtime.q_prescale(pb) > 0
+
+
+def _concurrent_stacks() -> bool:
+    """SR_CONCURRENT_STACKS=1 (read at every call): Aggregator._layer_plain's side stream; no pairing then."""
+    return os.environ.get("SR_CONCURRENT_STACKS", "0") == "1"
 
 
 def _wait(works):
