@@ -212,6 +212,20 @@ class Aggregator(nn.Module):
                     out[l, b, a] = torch.randperm(n_patch, generator=self.generator)[:rank].numpy()
         return out
 
+    def plan_subsample(self, fix_rank: Optional[int], B: int, na: int, n_patch: int) -> np.ndarray:
+        """The forward's draws in the reference's order (aggregator.py:580-626): the rank (``fix_rank``
+        clipped to the patch count, else drawn), then every layer's selection -> [depth, B, na, rank];
+        sets ``rank`` and ``last_subsample_indices``.  The inference and the training forward both
+        draw here, so the generator advances identically on either path."""
+        if fix_rank is not None:
+            self.rank = min(fix_rank, n_patch)
+        else:
+            lo, hi = min(self.min_rank, n_patch // 2), max(self.min_rank, n_patch // 2)
+            self.rank = int(torch.randint(lo, hi, (1,), generator=self.generator).item())
+        idx = self.draw_subsample(self.depth, B, na, n_patch, self.rank)
+        self.last_subsample_indices = torch.from_numpy(idx)
+        return idx
+
     # ------------------------------------------------------------------ multi-GPU
     def set_frame_sharding(self, group=None):
         """Shard frames across the ranks of ``group`` (torch.distributed, RCCL on ROCm).
@@ -365,12 +379,7 @@ class Aggregator(nn.Module):
         if C_in != 3:
             raise ValueError(f"Expected 3 input channels, got {C_in}")
         runtime.require_device(images, "Aggregator")
-        if sorted(list(no_reloc_list) + list(reloc_list)) != list(range(S)):
-            raise ValueError("no_reloc_list and reloc_list must be disjoint and cover every frame "
-                             f"(S={S}, got {list(no_reloc_list)} / {list(reloc_list)}); the reference's "
-                             "block mask (aggregator.py:302-311) assumes the same")
-        if num_recon == 0:
-            raise ValueError("at least one anchor (no_reloc) frame is required")
+        check_frame_lists(no_reloc_list, reloc_list, S)
         ps = self.patch_size
         assert H % ps == 0 and W % ps == 0, f"image size {H}x{W} is not a multiple of the patch size {ps}"
         group, G, r = self._world()
@@ -415,28 +424,18 @@ class Aggregator(nn.Module):
             work (so the subsample draws overlap DINO): the frame types (aggregator.py:287-299, by
             ORIGINAL frame index), the anchors' camera-token rows and the per-layer subsample row maps
             (aggregator.py:277-285, 580-626).  Returns the frame-type view."""
-            if fix_rank is not None:
-                self.rank = min(fix_rank, n_patch)
-            else:
-                lo, hi = min(self.min_rank, n_patch // 2), max(self.min_rank, n_patch // 2)
-                self.rank = int(torch.randint(lo, hi, (1,), generator=self.generator).item())
-            Pp = min(self.rank + psi, P)
             # the reference draws at every layer even without queries (select_scene_repe_for_reloc,
             # aggregator.py:351-357), so the generator advances identically
-            idx = self.draw_subsample(self.depth, B, Na, n_patch, self.rank)  # every rank draws all anchors
-            self.last_subsample_indices = torch.from_numpy(idx)
+            idx = self.plan_subsample(fix_rank, B, Na, n_patch)  # every rank draws all anchors
+            Pp = min(self.rank + psi, P)
             ftype = np.array(sum(([0 if a == 0 else 1 for a in my_anchors] + [2] * Nq_l for _ in range(B)), []),
                              dtype=np.int32)
             anchors, queries = camera_row_tables(B, Na_l, Nq_l, P)
             if not camera:
                 queries = queries[:0]
             parts = [ftype, anchors, queries]
-            if need_sub:
-                idx = idx[:, :, a_start:a_start + Na_l]                       # this rank's anchors
-                base = (np.arange(B) * S_l * P)[None, :, None, None] + (np.arange(Na_l) * P)[None, None, :, None]
-                sel = base + psi + idx                                        # [depth, B, Na_l, rank]
-                spec = np.broadcast_to(base + np.arange(psi)[None, None, None, :], (self.depth, B, Na_l, psi))
-                parts.append(np.concatenate([spec, sel], axis=-1).astype(np.int32).reshape(-1))
+            if need_sub:  # this rank's anchors
+                parts.append(subsample_rowmap(idx[:, :, a_start:a_start + Na_l], S_l, P, psi).reshape(-1))
             buf = runtime.to_device(torch.from_numpy(np.concatenate(parts)), dev)
             n0, n1 = len(ftype), len(ftype) + len(anchors)
             n2 = n1 + len(queries)
@@ -1015,6 +1014,28 @@ def shard_range(n: int, G: int, r: int) -> Tuple[int, int]:
     ranks own one frame more than the rest (counts differ by at most one)."""
     base, extra = divmod(n, G)
     return r * base + min(r, extra), base + (1 if r < extra else 0)
+
+
+def check_frame_lists(no_reloc_list, reloc_list, S: int) -> None:
+    """The anchor and query lists of a forward over S frames (inference and training alike)."""
+    if sorted(list(no_reloc_list) + list(reloc_list)) != list(range(S)):
+        raise ValueError("no_reloc_list and reloc_list must be disjoint and cover every frame "
+                         f"(S={S}, got {list(no_reloc_list)} / {list(reloc_list)}); the reference's "
+                         "block mask (aggregator.py:302-311) assumes the same")
+    if len(no_reloc_list) == 0:
+        raise ValueError("at least one anchor (no_reloc) frame is required")
+
+
+def subsample_rowmap(idx: np.ndarray, frames: int, P: int, psi: int) -> np.ndarray:
+    """Rows of x that each layer's anchor subsample reads (aggregator.py:277-285, 580-626): per anchor
+    frame its ``psi`` special rows, then the selected patch rows.  ``idx`` [depth, B, na, rank] patch
+    draws (plan_subsample); x holds ``frames`` frames of P rows per batch item, anchors first
+    -> int32 [depth, B, na * (psi + rank)]."""
+    depth, B, na, rank = idx.shape
+    base = (np.arange(B) * frames * P)[None, :, None, None] + (np.arange(na) * P)[None, None, :, None]
+    sel = base + psi + idx
+    spec = np.broadcast_to(base + np.arange(psi)[None, None, None, :], (depth, B, na, psi))
+    return np.concatenate([spec, sel], axis=-1).astype(np.int32).reshape(depth, B, na * (psi + rank))
 
 
 def camera_row_tables(B: int, Na: int, Nq: int, P: int) -> Tuple[np.ndarray, np.ndarray]:

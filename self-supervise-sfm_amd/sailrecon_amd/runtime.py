@@ -240,15 +240,17 @@ def kv_params(pb: PackedBlock, rope: Optional[Tuple[Tensor, Tensor]], **pos) -> 
     return d
 
 
-def kv_gemm(pb: PackedBlock, xn: Tensor, out: Tensor, kv_epi: Optional[dict]) -> None:
+def kv_gemm(pb: PackedBlock, xn: Tensor, out: Tensor, kv_epi: Optional[dict], aux: Optional[Tensor] = None) -> None:
     """K/V-only projection (qkv weight rows C..3C) with k-norm + RoPE on the K half (``kv_epi``:
-    kv_params; None: plain bias)."""
+    kv_params; None: plain bias).  ``aux``: keeps the pre-norm k|v beside ``out`` (the training tape;
+    without an epilogue ``out`` is the pre-norm k|v)."""
     C = pb.dim
     bias = None if pb.b_qkv is None else pb.b_qkv[C:3 * C]
     if kv_epi is None:
         ops.gemm(xn, pb.w_qkv[C:], out, _lib.SR_EPI_BIAS, bias=bias, tag="gemm")
     else:
-        ops.gemm(xn, pb.w_qkv[C:], out, _lib.SR_EPI_QKV, bias=bias, qkv=kv_epi, tag="gemm")
+        ops.gemm(xn, pb.w_qkv[C:], out, _lib.SR_EPI_QKV, bias=bias, qkv=kv_epi, tag="gemm",
+                 **({} if aux is None else dict(aux=aux)))
 
 
 # Residual updates folded into the next LayerNorm (VERDICT r3 item 3).  The reference's autocast

@@ -44,8 +44,25 @@ def _storage(t: torch.Tensor) -> int:
     return t.untyped_storage().data_ptr()
 
 
+def name_fields(names: dict, prefix: str, obj) -> None:
+    """``prefix.<field>`` for every tensor field of a dataclass (a packed block, a backward pack, a tape)."""
+    for f in dataclasses.fields(obj):
+        t = getattr(obj, f.name)
+        if isinstance(t, torch.Tensor):
+            names[_storage(t)] = f"{prefix}.{f.name}"
+
+
+def name_workspace(names: dict, ws, prefix: str = "") -> None:
+    """A runtime.Workspace's buffers by their workspace names."""
+    for name, t in ws._bufs.items():
+        names[_storage(t)] = prefix + name
+
+
 class Recorder:
-    """Stands in for the ops module: records the normalised (name, args, keywords) of every call."""
+    """Stands in for the ops module: records the normalised (name, args, keywords) of every call.
+    A subclass names further buffers (``_names``) and answers further helpers (tests/train_trace.py)."""
+
+    PURE = PURE
 
     def __init__(self, agg):
         self.calls, self.agg = [], agg
@@ -67,7 +84,7 @@ class Recorder:
         return t
 
     def __getattr__(self, fn):
-        if fn in PURE:
+        if fn in self.PURE:
             return getattr(real_ops, fn)
         if fn.startswith("__"):
             raise AttributeError(fn)
@@ -99,12 +116,8 @@ class Recorder:
         for stack in STACKS:
             for l, blk in enumerate(getattr(agg, stack)):
                 for pb in blk._packed.values():
-                    for f in dataclasses.fields(pb):
-                        t = getattr(pb, f.name)
-                        if isinstance(t, torch.Tensor):
-                            names[_storage(t)] = f"{stack}.{l}.{f.name}"
-        for name, t in agg._ws._bufs.items():
-            names[_storage(t)] = name
+                    name_fields(names, f"{stack}.{l}", pb)
+        name_workspace(names, agg._ws)
         return names
 
     def _tensor(self, t: torch.Tensor, names: dict) -> list:
