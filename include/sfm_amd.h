@@ -690,6 +690,53 @@ typedef struct sr_imc_loss_desc {
 int64_t sr_imc_loss_workspace(int n_views, int n_pairs, int n_points, int n_nodes, int num_bins);
 int sr_imc_loss(sr_stream_t stream, const sr_imc_loss_desc* desc);
 
+/* Residual diagnostics of the IMC loss (ABI 1.10): what compute_loss hands to plot_cdf_pdf_curves
+ * with do_record (train/train_imc.py:257-266, 413-425: CDFLossIndexPytorch.get_frame_statistics,
+ * train/losses/cdf_loss.py:245-259) and, in place of sanity_check_relative_poses' figure
+ * (train_imc.py:371), the residuals the loss bins, in pixels, with per-pair order statistics.
+ * `g` is read exactly as sr_imc_loss reads it, through the same kernels (loss, d_enc, grad_scale and
+ * workspace are ignored and may be NULL).  Three residuals per point, fp32 pixels:
+ *   v = 0  exact reprojection |K_d (T X) / (p_z + 1e-6) - x'|      (geometry.py:89-190)
+ *   v = 1  fixed-depth variant, divided by dst_depth + 1e-6           (geometry.py:193-303)
+ *   v = 2  Sampson distance |x'^T F x| / sqrt((Fx)_0^2 + (Fx)_1^2 + (F^T x')_0^2 + (F^T x')_1^2),
+ *          x = (u, v, 1) src, x' = (u', v', 1) dst, F = K_d^-T [t]x R K_s^-1 of (R | t) = the top
+ *          3x4 of T = E_d E_s^-1, formed in double, scaled to unit Frobenius norm, stored fp32;
+ *          NaN on every point of a pair with src_idx == dst_idx (a rule on the indices)
+ * Every output pointer is optional (NULL = skip), at least one must be given.
+ *   residuals    [3][n_pairs][n_points]
+ *   frame_pmf / frame_cdf / frame_pdf   [2][n_nodes][num_bins] (v = 0, 1): the arrays the loss looks
+ *                its values up in; pmf = hist / (total + 1e-10) (cdf_loss.py:182), cdf / pdf of
+ *                compute_weighted_pdf_cdf_vectorized (cdf_loss.py:123-189); specified for finite inputs
+ *   pair_counts  [3][n_pairs][2 + n_thresh]: n_finite (residual finite, a test on the bits), n_behind
+ *                (exact residual finite and p_z <= 0; the same number in every v), then per threshold the
+ *                finite points with r < thresh[t]; thresh is a device array of n_thresh <= 8 pixels
+ *   pair_stats   [3][n_pairs][4]: mean (fp64 sum in a fixed order, rounded once), median, p90, max over
+ *                the finite points.  With the n finite values ascending s[0..n-1]: median = s[(n-1)/2],
+ *                p90 = s[(9n+9)/10 - 1], exact elements of `residuals` found by a radix select on the
+ *                bit patterns; n = 0 gives four quiet NaNs
+ * No float atomics beyond the loss's exact histogram counts: every output is bit-stable. */
+typedef struct sr_imc_stats_desc {
+  float* residuals;
+  float* frame_pmf;
+  float* frame_cdf;
+  float* frame_pdf;
+  const float* thresh;
+  int n_thresh;
+  uint32_t* pair_counts;
+  float* pair_stats;
+  float* workspace;          /* >= sr_imc_stats_workspace(...) floats */
+  int64_t workspace_floats;  /* its size, checked */
+} sr_imc_stats_desc;
+
+/* 0 for a non-positive size. */
+int64_t sr_imc_stats_workspace(int n_views, int n_pairs, int n_points, int n_nodes, int num_bins);
+/* One memset and up to seven launches, asynchronous and allocation-free.  SR_EINVAL for the
+ * arguments sr_imc_loss refuses (a null input pointer, n_views outside [1, 64], num_bins outside
+ * [3, 1024], taps wider than the bins, an empty range or image, n_pairs / n_points / n_nodes <= 0),
+ * n_pairs > 65535, n_thresh outside [0, 8], n_thresh > 0 with thresh or pair_counts NULL, a
+ * missing or undersized workspace, or every output NULL. */
+int sr_imc_residual_stats(sr_stream_t stream, const sr_imc_loss_desc* g, const sr_imc_stats_desc* s);
+
 /* ------------------------------------------------------------------------
  * LayerNorm over the last dim of fp32 rows (block.py:50,70; camera_head.py:64-77;
  * vision_transformer.py:192,300).  out_row r = LN(x[rowmap ? rowmap[r] : r]).

@@ -9,6 +9,7 @@
 //   abi_host_check layout corres   the same for the structs of sr_corres_sample (ABI 1.6), apart:
 //                           tests/test_debug_build.py pins the set the plain mode prints
 //   abi_host_check layout pose_eval   the same for the structs of sr_pose_pair_errors / sr_pose_align (ABI 1.9)
+//   abi_host_check layout imc_stats   the same for sr_imc_stats_desc (ABI 1.10)
 //   abi_host_check check    the validation sweep; exit 0 iff every call returned what it should
 #include <cstddef>
 #include <cstdio>
@@ -140,6 +141,17 @@ void layout_pose_eval() {
           FIELD(sr_pose_align_desc, gt_stride), FIELD(sr_pose_align_desc, n_views),
           FIELD(sr_pose_align_desc, with_scale), FIELD(sr_pose_align_desc, out), FIELD(sr_pose_align_desc, status),
           FIELD(sr_pose_align_desc, err)));
+  std::printf("}\n");
+}
+
+void layout_imc_stats() {
+  const char* sep = "";
+  std::printf("{");
+  STRUCT(sr_imc_stats_desc,
+         (FIELD(sr_imc_stats_desc, residuals), FIELD(sr_imc_stats_desc, frame_pmf), FIELD(sr_imc_stats_desc, frame_cdf),
+          FIELD(sr_imc_stats_desc, frame_pdf), FIELD(sr_imc_stats_desc, thresh), FIELD(sr_imc_stats_desc, n_thresh),
+          FIELD(sr_imc_stats_desc, pair_counts), FIELD(sr_imc_stats_desc, pair_stats),
+          FIELD(sr_imc_stats_desc, workspace), FIELD(sr_imc_stats_desc, workspace_floats)));
   std::printf("}\n");
 }
 
@@ -409,6 +421,50 @@ void check() {
     expect("sr_imc_loss null node_src", sr_imc_loss(nullptr, &b), false);
     b = ld, b.max_val = 0.f;
     expect("sr_imc_loss empty range", sr_imc_loss(nullptr, &b), false);
+
+    // ABI 1.10: the same geometry with the loss's own outputs absent, and every rejection the header lists
+    sr_imc_loss_desc g = ld;
+    g.loss = nullptr, g.d_enc = nullptr, g.workspace = nullptr, g.n_points = 10000;
+    const int64_t need = sr_imc_stats_workspace(g.n_views, g.n_pairs, g.n_points, g.n_nodes, g.num_bins);
+    std::printf("imc stats workspace floats: %lld\n", (long long)need);
+    if (need < 4LL * 70 * 10000 || sr_imc_stats_workspace(0, 70, 10000, 64, 1024) != 0 ||
+        sr_imc_stats_workspace(64, 70, 0, 64, 1024) != 0)
+      ++g_fail;
+    sr_imc_stats_desc sd{};
+    sd.residuals = fake<float>(14), sd.frame_pmf = fake<float>(15), sd.frame_cdf = fake<float>(16);
+    sd.frame_pdf = fake<float>(17), sd.thresh = fake<float>(18), sd.n_thresh = 8, sd.pair_counts = fake<uint32_t>(19);
+    sd.pair_stats = fake<float>(20), sd.workspace = fake<float>(21), sd.workspace_floats = need;
+    expect("sr_imc_residual_stats every output", sr_imc_residual_stats(nullptr, &g, &sd), true);
+    sr_imc_stats_desc c{};
+    c.pair_stats = fake<float>(20), c.workspace = fake<float>(21), c.workspace_floats = need;
+    expect("sr_imc_residual_stats pair_stats only", sr_imc_residual_stats(nullptr, &g, &c), true);
+    expect("sr_imc_residual_stats null g", sr_imc_residual_stats(nullptr, nullptr, &sd), false);
+    expect("sr_imc_residual_stats null s", sr_imc_residual_stats(nullptr, &g, nullptr), false);
+    c = sd, c.n_thresh = 9;
+    expect("sr_imc_residual_stats 9 thresholds", sr_imc_residual_stats(nullptr, &g, &c), false);
+    c = sd, c.n_thresh = -1;
+    expect("sr_imc_residual_stats -1 thresholds", sr_imc_residual_stats(nullptr, &g, &c), false);
+    c = sd, c.thresh = nullptr;
+    expect("sr_imc_residual_stats null thresh", sr_imc_residual_stats(nullptr, &g, &c), false);
+    c = sd, c.pair_counts = nullptr;
+    expect("sr_imc_residual_stats thresholds without counts", sr_imc_residual_stats(nullptr, &g, &c), false);
+    c = sd, c.workspace = nullptr;
+    expect("sr_imc_residual_stats null workspace", sr_imc_residual_stats(nullptr, &g, &c), false);
+    c = sd, c.workspace_floats = need - 1;
+    expect("sr_imc_residual_stats workspace one float short", sr_imc_residual_stats(nullptr, &g, &c), false);
+    c = sr_imc_stats_desc{}, c.workspace = fake<float>(21), c.workspace_floats = need;
+    expect("sr_imc_residual_stats every output NULL", sr_imc_residual_stats(nullptr, &g, &c), false);
+    b = g, b.n_views = 65;
+    expect("sr_imc_residual_stats 65 views", sr_imc_residual_stats(nullptr, &b, &sd), false);
+    b = g, b.num_bins = 1025;
+    expect("sr_imc_residual_stats 1025 bins", sr_imc_residual_stats(nullptr, &b, &sd), false);
+    b = g, b.n_points = 0;
+    expect("sr_imc_residual_stats 0 points", sr_imc_residual_stats(nullptr, &b, &sd), false);
+    b = g, b.dst_coords = nullptr;
+    expect("sr_imc_residual_stats null dst_coords", sr_imc_residual_stats(nullptr, &b, &sd), false);
+    b = g, b.n_pairs = 65536;
+    c = sd, c.workspace_floats = sr_imc_stats_workspace(b.n_views, b.n_pairs, b.n_points, b.n_nodes, b.num_bins);
+    expect("sr_imc_residual_stats 65536 pairs", sr_imc_residual_stats(nullptr, &b, &c), false);
   }
   expect("sr_corres_sample null", sr_corres_sample(nullptr, nullptr), false);
   {  // ABI 1.6: null pointers, empty sizes and an undersized workspace are refused before any launch
@@ -582,6 +638,8 @@ int main(int argc, char** argv) {
       layout_corres();
     else if (argc > 2 && std::string(argv[2]) == "pose_eval")
       layout_pose_eval();
+    else if (argc > 2 && std::string(argv[2]) == "imc_stats")
+      layout_imc_stats();
     else
       layout();
     return 0;

@@ -15,6 +15,12 @@
 //   imc_final_kernel   partials summed in fixed order -> per-pair -> per-view grads -> shared
 //                      focal / K' / FoV / quaternion backward -> d enc; the loss value
 // Points are float32 like the reference; the 3x3 / 4x4 algebra runs in double.
+//
+// sr_imc_residual_stats (ABI 1.10) reports what the loss bins, through the same kernels: views,
+// pairs (+ the fundamental matrix), points (+ the three residuals in pixels), cdf, then
+//   imc_frames_kernel  per (variant, node): pmf / cdf / pdf copied out of the workspace
+//   imc_select_kernel  per (variant, pair): counts, fp64 mean, max and the exact median / p90 by a
+//                      radix select on the fp32 bit patterns (4 digits of 8 bits, histograms in LDS)
 #include <cmath>
 
 #include "sr_common.h"
@@ -143,7 +149,8 @@ __global__ void imc_views_kernel(sr_imc_loss_desc d, float* wsp) {
 }
 
 // ---------------------------------------------------------------- pairs
-__global__ void imc_pairs_kernel(sr_imc_loss_desc d, float* wsp) {
+// fmat (stats only, else NULL): [n_pairs][9] F = Kd^-T [t]x R Ks^-1 of T = (R | t), unit Frobenius norm
+__global__ void imc_pairs_kernel(sr_imc_loss_desc d, float* wsp, float* fmat) {
   const Ws w = carve(wsp, d.n_views, d.n_pairs, d.n_nodes, d.num_bins);
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= d.n_pairs) return;
@@ -163,15 +170,44 @@ __global__ void imc_pairs_kernel(sr_imc_loss_desc d, float* wsp) {
     o[t] = (float)Ksi[t];
     o[9 + t] = vd[t];
   }
+  double T[12];
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 4; ++j) {
       double s = 0;
       for (int t = 0; t < 4; ++t) s += Ed[i * 4 + t] * Esi[t * 4 + j];
+      T[i * 4 + j] = s;
       o[18 + i * 4 + j] = (float)s;
     }
   for (int t = 0; t < 16; ++t) {
     o[30 + t] = (float)Esi[t];
     o[46 + t] = (float)Ed[t];
+  }
+  if (fmat) {
+    double Kd[9], Kdi[9], E[9], A[9], F[9];
+    for (int t = 0; t < 9; ++t) Kd[t] = vd[t];
+    mat3_inv(Kd, Kdi);
+    const double tx = T[3], ty = T[7], tz = T[11];
+    for (int j = 0; j < 3; ++j) {  // [t]x R
+      E[j] = ty * T[8 + j] - tz * T[4 + j];
+      E[3 + j] = tz * T[j] - tx * T[8 + j];
+      E[6 + j] = tx * T[4 + j] - ty * T[j];
+    }
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) {
+        double a = 0;
+        for (int t = 0; t < 3; ++t) a += Kdi[t * 3 + i] * E[t * 3 + j];  // Kd^-T E
+        A[i * 3 + j] = a;
+      }
+    double n2 = 0;
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) {
+        double a = 0;
+        for (int t = 0; t < 3; ++t) a += A[i * 3 + t] * Ksi[t * 3 + j];
+        F[i * 3 + j] = a;
+        n2 += a * a;
+      }
+    const double inv = 1.0 / sqrt(n2);
+    for (int t = 0; t < 9; ++t) fmat[(int64_t)p * 9 + t] = (float)(F[t] * inv);
   }
 }
 
@@ -202,12 +238,42 @@ __device__ inline PointGeo point_geo(const sr_imc_loss_desc& d, const float* pr,
   return g;
 }
 
+// a test on the bits: the library builds with -fno-honor-nans
+__device__ inline bool finite_bits(uint32_t b) { return (b & 0x7f800000u) != 0x7f800000u; }
+constexpr uint32_t QNAN_BITS = 0x7fc00000u;
+
+struct StatsOut {  // sr_imc_residual_stats only
+  const float* fmat;  // [n_pairs][9]
+  float* resid;       // [3][n_pairs][n_points] pixels: exact, fixed depth, Sampson
+  float* behind;      // [n_pairs][n_points] 1 where the exact residual is finite and p_z <= 0, else 0
+};
+
 // ---------------------------------------------------------------- residuals + histograms
-__global__ __launch_bounds__(PTB) void imc_points_kernel(sr_imc_loss_desc d, float* wsp) {
+template <bool kStats>
+__global__ __launch_bounds__(PTB) void imc_points_kernel(sr_imc_loss_desc d, float* wsp, StatsOut so) {
   const Ws w = carve(wsp, d.n_views, d.n_pairs, d.n_nodes, d.num_bins);
   const int p = blockIdx.y, k = blockIdx.x * PTB + threadIdx.x;
   if (k >= d.n_points) return;
   const PointGeo g = point_geo(d, w.pairs + (int64_t)p * PAIR_SLOTS, p, k);
+  if constexpr (kStats) {
+    const int64_t e = (int64_t)p * d.n_points + k, pk = (int64_t)d.n_pairs * d.n_points;
+    so.resid[e] = g.r[0];
+    so.resid[pk + e] = g.r[1];
+    so.behind[e] = finite_bits(__float_as_uint(g.r[0])) && g.p[2] <= 0.f ? 1.f : 0.f;
+    float r2 = __uint_as_float(QNAN_BITS);  // src == dst: no epipolar geometry (a rule on the indices)
+    if (d.src_idx[p] != d.dst_idx[p]) {
+      // Sampson distance of x = (u, v, 1), x' = (u', v', 1) under the pair's F; sums in double
+      const float* F = so.fmat + (int64_t)p * 9;
+      const double u = d.src_coords[2 * e], v = d.src_coords[2 * e + 1];
+      const double ox = d.dst_coords[2 * e], oy = d.dst_coords[2 * e + 1];
+      double Fx[3], Ft[2];
+      for (int i = 0; i < 3; ++i) Fx[i] = (double)F[i * 3] * u + (double)F[i * 3 + 1] * v + (double)F[i * 3 + 2];
+      for (int j = 0; j < 2; ++j) Ft[j] = (double)F[j] * ox + (double)F[3 + j] * oy + (double)F[6 + j];
+      const double num = ox * Fx[0] + oy * Fx[1] + Fx[2];
+      r2 = (float)(fabs(num) / sqrt(Fx[0] * Fx[0] + Fx[1] * Fx[1] + Ft[0] * Ft[0] + Ft[1] * Ft[1]));
+    }
+    so.resid[2 * pk + e] = r2;
+  }
   const float bw = (d.max_val - d.min_val) / d.num_bins;
   const int ns = d.node_src[p], nd = d.node_dst[p];
   for (int vv = 0; vv < 2; ++vv) {
@@ -443,6 +509,135 @@ __global__ void imc_final_kernel(sr_imc_loss_desc d, float* wsp, int chunks) {
   }
 }
 
+// ---------------------------------------------------------------- stats: per-frame arrays
+__global__ void imc_frames_kernel(sr_imc_loss_desc d, float* wsp, float* pmf, float* cdf, float* pdf) {
+  const Ws w = carve(wsp, d.n_views, d.n_pairs, d.n_nodes, d.num_bins);
+  const int vv = blockIdx.y, node = blockIdx.x, nb = d.num_bins;
+  const int64_t o = ((int64_t)vv * d.n_nodes + node) * nb;
+  const float t = w.tot[vv * d.n_nodes + node] + 1e-10f;  // as imc_cdf_kernel
+  for (int i = threadIdx.x; i < nb; i += blockDim.x) {
+    if (pmf) pmf[o + i] = w.hist[o + i] / t;
+    if (cdf) cdf[o + i] = w.cdf[o + i];
+    if (pdf) pdf[o + i] = w.pdf[o + i];
+  }
+}
+
+// ---------------------------------------------------------------- stats: per-pair selection
+constexpr int SEL_T = 1024;       // threads of the one workgroup per (variant, pair)
+constexpr int SEL_CACHE = 12288;  // residuals of a pair kept in LDS (48 KiB); more are re-read from global memory
+
+__device__ inline double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// Non-negative floats order as their bit patterns, so rank k of the finite values is found digit by
+// digit: a 256-bin histogram of the digit among the values that share the digits found so far, a
+// scan for the bin that holds rank k, four times.  Both ranks (median, p90) ride the same passes,
+// each with its own prefix and histogram; the first pass also takes the counts, the max and the sum.
+__global__ __launch_bounds__(SEL_T) void imc_select_kernel(const float* resid, const float* behind, int n_pairs,
+                                                           int n_points, const float* thresh, int n_thresh,
+                                                           uint32_t* counts, float* stats) {
+  __shared__ uint32_t cache[SEL_CACHE];
+  __shared__ uint32_t hist[2][256];
+  __shared__ double wsum[SEL_T / 64];
+  __shared__ uint32_t cnt[2 + 8];
+  __shared__ uint32_t smax;
+  __shared__ uint32_t prefix[2];
+  __shared__ uint64_t rank[2];
+  const int p = blockIdx.x, v = blockIdx.y, tid = threadIdx.x;
+  const uint32_t* x = reinterpret_cast<const uint32_t*>(resid) + ((int64_t)v * n_pairs + p) * n_points;
+  const float* bh = behind + (int64_t)p * n_points;
+  const bool cached = n_points <= SEL_CACHE;
+  if (tid < 512) hist[tid >> 8][tid & 255] = 0;
+  if (tid < 10) cnt[tid] = 0;
+  if (tid == 0) smax = 0;
+  __syncthreads();
+  float th[8];
+#pragma unroll
+  for (int t = 0; t < 8; ++t) th[t] = t < n_thresh ? thresh[t] : 0.f;
+  uint32_t c_fin = 0, c_beh = 0, c_th[8] = {0, 0, 0, 0, 0, 0, 0, 0}, mx = 0;
+  double s = 0;
+  for (int k = tid; k < n_points; k += SEL_T) {  // a fixed assignment of points to threads: a fixed sum
+    const uint32_t b = x[k];
+    if (cached) cache[k] = b;
+    if (finite_bits(b)) {
+      const float f = __uint_as_float(b);
+      ++c_fin;
+      s += (double)f;
+      mx = b > mx ? b : mx;
+#pragma unroll
+      for (int t = 0; t < 8; ++t) c_th[t] += (t < n_thresh && f < th[t]) ? 1u : 0u;
+      atomicAdd(&hist[0][b >> 24], 1u);
+    }
+    c_beh += bh[k] != 0.f ? 1u : 0u;
+  }
+  if (c_fin) atomicAdd(&cnt[0], c_fin);
+  if (c_beh) atomicAdd(&cnt[1], c_beh);
+#pragma unroll
+  for (int t = 0; t < 8; ++t)
+    if (c_th[t]) atomicAdd(&cnt[2 + t], c_th[t]);
+  if (mx) atomicMax(&smax, mx);
+  s = wave_sum_f64(s);
+  if ((tid & 63) == 0) wsum[tid >> 6] = s;
+  __syncthreads();
+  const uint32_t n = cnt[0];
+  const int64_t slot = (int64_t)v * n_pairs + p;
+  if (tid == 0 && counts) {
+    uint32_t* c = counts + slot * (2 + n_thresh);
+    c[0] = n;
+    c[1] = cnt[1];
+    for (int t = 0; t < n_thresh; ++t) c[2 + t] = cnt[2 + t];
+  }
+  if (!stats) return;
+  float* out = stats + slot * 4;
+  if (n == 0) {  // uniform: n comes from LDS after the barrier
+    if (tid < 4) out[tid] = __uint_as_float(QNAN_BITS);
+    return;
+  }
+  if (tid == 0) {
+    double tot = 0;
+    for (int q = 0; q < SEL_T / 64; ++q) tot += wsum[q];
+    out[0] = (float)(tot / (double)n);
+    out[3] = __uint_as_float(smax);
+  }
+  if (tid < 2) {
+    prefix[tid] = 0;
+    rank[tid] = tid == 0 ? ((uint64_t)n - 1) / 2 : (9ull * n + 9) / 10 - 1;  // lower median; p90
+  }
+  __syncthreads();
+  for (int dgt = 0; dgt < 4; ++dgt) {
+    if (tid < 2) {  // the bin of this rank among the values that share its prefix
+      const uint32_t* h = hist[dgt == 0 ? 0 : tid];
+      uint64_t r = rank[tid];
+      int b = 0;
+      for (; b < 255; ++b) {
+        const uint32_t c = h[b];
+        if (r < c) break;
+        r -= c;
+      }
+      rank[tid] = r;
+      prefix[tid] = (prefix[tid] << 8) | (uint32_t)b;
+    }
+    __syncthreads();
+    if (dgt == 3) break;
+    if (tid < 512) hist[tid >> 8][tid & 255] = 0;
+    __syncthreads();
+    const int hi = 24 - 8 * dgt, lo = hi - 8;  // digits found so far: bits >= hi; this pass: bits [lo, hi)
+    const uint32_t p0 = prefix[0], p1 = prefix[1];
+    for (int k = tid; k < n_points; k += SEL_T) {
+      const uint32_t b = cached ? cache[k] : x[k];
+      if (!finite_bits(b)) continue;
+      const uint32_t top = b >> hi, d8 = (b >> lo) & 255u;
+      if (top == p0) atomicAdd(&hist[0][d8], 1u);
+      if (top == p1) atomicAdd(&hist[1][d8], 1u);
+    }
+    __syncthreads();
+  }
+  if (tid < 2) out[1 + tid] = __uint_as_float(prefix[tid]);
+}
+
 }  // namespace
 
 extern "C" int64_t sr_imc_loss_workspace(int n_views, int n_pairs, int n_points, int n_nodes, int num_bins) {
@@ -469,10 +664,63 @@ extern "C" int sr_imc_loss(sr_stream_t stream, const sr_imc_loss_desc* desc) {
   SR_CHECK(hipMemsetAsync(w + hist_off, 0, (2 * nn * nb + 2 * nn) * sizeof(float), s) == hipSuccess, SR_ELAUNCH,
            "sr_imc_loss: memset");
   hipLaunchKernelGGL(imc_views_kernel, dim3(1), dim3(64), 0, s, d, w);
-  hipLaunchKernelGGL(imc_pairs_kernel, dim3((d.n_pairs + 63) / 64), dim3(64), 0, s, d, w);
-  hipLaunchKernelGGL(imc_points_kernel, dim3(chunks, d.n_pairs), dim3(PTB), 0, s, d, w);
+  hipLaunchKernelGGL(imc_pairs_kernel, dim3((d.n_pairs + 63) / 64), dim3(64), 0, s, d, w, (float*)nullptr);
+  hipLaunchKernelGGL(imc_points_kernel<false>, dim3(chunks, d.n_pairs), dim3(PTB), 0, s, d, w, StatsOut{});
   hipLaunchKernelGGL(imc_cdf_kernel, dim3(d.n_nodes, 2), dim3(256), 0, s, d, w);
   hipLaunchKernelGGL(imc_back_kernel, dim3(chunks, d.n_pairs), dim3(PTB), 0, s, d, w, chunks);
   hipLaunchKernelGGL(imc_final_kernel, dim3(1), dim3(64), 0, s, d, w, chunks);
   return sr::check_launch("sr_imc_loss");
+}
+
+extern "C" int64_t sr_imc_stats_workspace(int n_views, int n_pairs, int n_points, int n_nodes, int num_bins) {
+  if (n_views <= 0 || n_pairs <= 0 || n_points <= 0 || n_nodes <= 0 || num_bins <= 0) return 0;
+  // the loss's carve-up without partial slots, then F, three residual planes and the behind flags
+  return ws_floats(n_views, n_pairs, n_nodes, num_bins, 0) + 9ll * n_pairs + 4ll * n_pairs * n_points;
+}
+
+extern "C" int sr_imc_residual_stats(sr_stream_t stream, const sr_imc_loss_desc* desc, const sr_imc_stats_desc* out) {
+  SR_CHECK(desc && out, SR_EINVAL, "sr_imc_residual_stats: null desc");
+  sr_imc_loss_desc d = *desc;
+  const sr_imc_stats_desc& o = *out;
+  SR_CHECK(d.enc && d.kp2k && d.src_idx && d.dst_idx && d.src_coords && d.dst_coords && d.src_depth && d.dst_depth &&
+               d.node_src && d.node_dst && d.smooth_w,
+           SR_EINVAL, "sr_imc_residual_stats: null pointer");
+  SR_CHECK(d.n_views > 0 && d.n_views <= 64 && d.n_pairs > 0 && d.n_points > 0 && d.n_nodes > 0 &&
+               d.num_bins > 2 && d.num_bins <= 1024 && d.smooth_radius >= 0 && 2 * d.smooth_radius + 1 <= d.num_bins &&
+               d.max_val > d.min_val && d.H > 0 && d.W > 0,
+           SR_EINVAL, "sr_imc_residual_stats: bad sizes (views <= 64, bins <= 1024)");
+  SR_CHECK(o.n_thresh >= 0 && o.n_thresh <= 8, SR_EINVAL, "sr_imc_residual_stats: n_thresh outside [0, 8]");
+  SR_CHECK(o.n_thresh == 0 || (o.thresh && o.pair_counts), SR_EINVAL,
+           "sr_imc_residual_stats: thresholds need thresh and pair_counts");
+  const bool frames = o.frame_pmf || o.frame_cdf || o.frame_pdf, select = o.pair_counts || o.pair_stats;
+  SR_CHECK(frames || select || o.residuals, SR_EINVAL, "sr_imc_residual_stats: every output is NULL");
+  const int64_t base = ws_floats(d.n_views, d.n_pairs, d.n_nodes, d.num_bins, 0);
+  const int64_t pk = (int64_t)d.n_pairs * d.n_points;
+  SR_CHECK(o.workspace && o.workspace_floats >= base + 9ll * d.n_pairs + 4 * pk, SR_EINVAL,
+           "sr_imc_residual_stats: workspace missing or smaller than sr_imc_stats_workspace");
+  SR_CHECK(d.n_pairs <= 65535, SR_EINVAL, "sr_imc_residual_stats: more than 65535 pairs");
+  hipStream_t s = (hipStream_t)stream;
+  const int chunks = (d.n_points + PTB - 1) / PTB;
+  float* w = o.workspace;
+  d.loss = nullptr, d.d_enc = nullptr, d.workspace = w, d.grad_scale = 0.f;  // ignored fields: nothing reads them
+  float* fmat = w + base;
+  float* resid = o.residuals ? o.residuals : fmat + 9ll * d.n_pairs;
+  float* behind = fmat + 9ll * d.n_pairs + 3 * pk;
+  const int64_t nn = d.n_nodes, nb = d.num_bins;
+  const int64_t hist_off = (int64_t)d.n_views * VIEW_SLOTS + (int64_t)d.n_pairs * PAIR_SLOTS;
+  SR_CHECK(hipMemsetAsync(w + hist_off, 0, (2 * nn * nb + 2 * nn) * sizeof(float), s) == hipSuccess, SR_ELAUNCH,
+           "sr_imc_residual_stats: memset");
+  hipLaunchKernelGGL(imc_views_kernel, dim3(1), dim3(64), 0, s, d, w);
+  hipLaunchKernelGGL(imc_pairs_kernel, dim3((d.n_pairs + 63) / 64), dim3(64), 0, s, d, w, fmat);
+  hipLaunchKernelGGL(imc_points_kernel<true>, dim3(chunks, d.n_pairs), dim3(PTB), 0, s, d, w,
+                     StatsOut{fmat, resid, behind});
+  if (frames) {
+    hipLaunchKernelGGL(imc_cdf_kernel, dim3(d.n_nodes, 2), dim3(256), 0, s, d, w);
+    hipLaunchKernelGGL(imc_frames_kernel, dim3(d.n_nodes, 2), dim3(256), 0, s, d, w, o.frame_pmf, o.frame_cdf,
+                       o.frame_pdf);
+  }
+  if (select)
+    hipLaunchKernelGGL(imc_select_kernel, dim3(d.n_pairs, 3), dim3(SEL_T), 0, s, resid, behind, d.n_pairs, d.n_points,
+                       o.thresh, o.n_thresh, o.pair_counts, o.pair_stats);
+  return sr::check_launch("sr_imc_residual_stats");
 }

@@ -125,6 +125,14 @@ class ImcLossDesc(ctypes.Structure):
     ]
 
 
+class ImcStatsDesc(ctypes.Structure):
+    """sr_imc_stats_desc (include/sfm_amd.h)."""
+    _fields_ = [
+        ("residuals", _vp), ("frame_pmf", _vp), ("frame_cdf", _vp), ("frame_pdf", _vp), ("thresh", _vp),
+        ("n_thresh", _i32), ("pair_counts", _vp), ("pair_stats", _vp), ("workspace", _vp), ("workspace_floats", _i64),
+    ]
+
+
 class CorresPair(ctypes.Structure):
     """sr_corres_pair (include/sfm_amd.h): one record of the device-resident pair table."""
     _fields_ = [
@@ -250,6 +258,8 @@ _PROTOS = {
     "sr_copy2d_f32": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32]),
     "sr_imc_loss_workspace": (_i64, [_i32, _i32, _i32, _i32, _i32]),
     "sr_imc_loss": (_i32, [_vp, ctypes.POINTER(ImcLossDesc)]),
+    "sr_imc_stats_workspace": (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    "sr_imc_residual_stats": (_i32, [_vp, ctypes.POINTER(ImcLossDesc), ctypes.POINTER(ImcStatsDesc)]),
     "sr_pose_act_bwd_f32": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32]),
     "sr_resize_crop_chw_f32": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "sr_corres_sample_workspace": (_i64, [_i32, _i32]),

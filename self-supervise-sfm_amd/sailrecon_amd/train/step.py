@@ -21,11 +21,12 @@ from typing import Dict, List, Optional, Tuple
 import torch
 import torch.distributed as dist
 
-from .loss import CDFLossIndexPytorch, imc_loss
+from .loss import CDFLossIndexPytorch, imc_loss, plot_data, residual_stats, stats_words, summarize
 from .model import TrainGraph
 from .optim import Adam, CosineWarmupScheduler, GradScaler
 
 Tensor = torch.Tensor
+MONITOR_THRESHOLDS = (1., 2., 4., 8.)  # pixels: the inlier@t keys of Trainer.step(monitor=True)
 
 
 def prepare_model_input(rgb: Tensor) -> Tuple[Tensor, List[int], List[int]]:
@@ -133,7 +134,10 @@ class Trainer:
 
     # ------------------------------------------------------------------ the step
     def step(self, images: Tensor, no_reloc_list: List[int], reloc_list: List[int], batch: dict,
-             fix_rank: int = 300) -> Dict[str, float]:
+             fix_rank: int = 300, do_record: bool = False, monitor: bool = False) -> Dict[str, float]:
+        """``monitor`` launches sr_imc_residual_stats after the loss and adds summarize's scalars
+        ("reproj/median_px", "sampson/inlier@2", ...) to the result; they come back in the loss's
+        own D2H copy.  ``do_record`` (train_imc.py:375-376) adds the reference's "plot_data"."""
         # the loss's batch tensors go to the device first, while the stream is idle: a host tensor's
         # copy blocks the host until the stream reaches it, so in the middle of the step it stalled the
         # launch queue behind the whole forward (imc_loss converts the same way; no-ops afterwards)
@@ -144,9 +148,16 @@ class Trainer:
         self._works, self._reduced = [], {}
         pose = self.graph.forward(images, no_reloc_list, reloc_list, fix_rank=fix_rank)
         H, W = images.shape[-2], images.shape[-1]
-        loss, d_enc = imc_loss(pose[0], (H, W), lb["K_prime_to_K"], bool(batch["shared_focal"]), lb["src_idx"],
-                               lb["dst_idx"], lb["src_coords"], lb["dst_coords"], lb["src_depth"],
-                               lb["dst_depth"], self.cdf, grad_scale=self.scaler.get_scale())
+        largs = (pose[0], (H, W), lb["K_prime_to_K"], bool(batch["shared_focal"]), lb["src_idx"], lb["dst_idx"],
+                 lb["src_coords"], lb["dst_coords"], lb["src_depth"], lb["dst_depth"], self.cdf)
+        stats = readback = None
+        if monitor or do_record:  # loss | pair_stats | pair_counts in one buffer: one copy reads all of it
+            readback = torch.empty(1 + stats_words(lb["src_coords"].shape[0], len(MONITOR_THRESHOLDS)), device=dev,
+                                   dtype=torch.float32)
+        loss, d_enc = imc_loss(*largs, grad_scale=self.scaler.get_scale(),
+                               loss_out=None if readback is None else readback[:1])
+        if readback is not None:
+            stats = residual_stats(*largs, thresholds=MONITOR_THRESHOLDS, pairs_out=readback[1:])
         self.graph.backward(d_enc[None])
         for w in self._works:
             w.wait()
@@ -157,7 +168,16 @@ class Trainer:
         self.scaler.update()
         lr = self.sched.step()
         self.steps_done += 1
-        return {"loss": float(loss.item()), "lr": lr, "skipped": found}
+        if readback is None:
+            return {"loss": float(loss.item()), "lr": lr, "skipped": found}
+        host = readback.cpu().numpy()
+        out = {"loss": float(host[0]), "lr": lr, "skipped": found}
+        summary = summarize(stats, host_pairs=host[1:])
+        if monitor:
+            out.update({f"{name}/{k}": v for name, r in summary.items() for k, v in r.items()})
+        if do_record:
+            out["plot_data"] = plot_data(stats, self.cdf, summary)
+        return out
 
     def save_checkpoint(self, checkpoint_dir, loss=None) -> Path:
         """Rank 0 saves (train_imc.py:426-428 guards the call with is_main_process)."""
