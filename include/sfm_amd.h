@@ -1033,6 +1033,59 @@ typedef struct sr_pose_align_desc {
  * buffer that is not 8-byte aligned. */
 int sr_pose_align(sr_stream_t stream, const sr_pose_align_desc* desc);
 
+/* ------------------------------------------------------------------------------------------
+ * Scoring point clouds (ABI 1.11): the nearest-neighbour distance of every query point to a target
+ * set, by brute force, with the histogram and the moments that accuracy / completeness / Chamfer
+ * distance and precision / recall / F-score at a threshold are read off on the host -- what the
+ * reference hands to its `eval` package (train/train_imc.py:301-317; absent from the reference tree).
+ * One call scores one direction.  Definitions: DESIGN.md "Scoring point clouds", csrc/sr_cloud_eval.hip.
+ *   transform  p' = fl32(s (R p) + t), every product and sum in fp64 (left to right, not contracted)
+ *              from the fp32 point and the fp64 transform, rounded once; the same for both sides
+ *   distance   d(q) = sqrt(min_t d2(q, t)), d2 = dx dx + dy dy + dz dz in fp32 from the direct
+ *              differences dx = q.x - t.x, ...; never |q|^2 + |t|^2 - 2 q.t, which loses every digit for
+ *              a cloud far from the origin relative to its point spacing
+ *   non-finite a target with a NaN or Inf component before or after its transform (a test on the bits)
+ *              is never selected.  A non-finite query, a query whose d2 overflows and a query without a
+ *              finite target get dist = NaN, index = -1 and count in hist[n_bins + 1] and stats[4].
+ *   index      the lowest target index that attains the kernel's own fp32 minimum of d2, whatever the
+ *              target split; two runs, and any two target_chunk values, give bit-identical dist, index,
+ *              hist and stats
+ *   hist       slot k < n_bins counts k <= fl32(d / bin_len) < k + 1, slot n_bins the larger distances,
+ *              slot n_bins + 1 the non-finite queries.  Integer atomics only.
+ *   stats      fp64 from the fp32 d in a fixed order (a lane's queries ascending, a fixed LDS tree, one
+ *              partial per workgroup, one workgroup summing the partials in ascending runs); no
+ *              floating-point atomics anywhere
+ * ------------------------------------------------------------------------------------------ */
+typedef struct sr_cloud_nn_desc {
+  const float* query;         /* [n_query][3] fp32, packed */
+  const float* target;        /* [n_target][3] fp32, packed */
+  int64_t n_query, n_target;  /* 1 .. 2^31 - 1 each */
+  const double* query_xform;  /* device [13]: scale, R row-major, t -- sr_pose_align's out[0..12] as it lies -- or NULL */
+  const double* target_xform; /* likewise for the targets, or NULL */
+  int target_chunk;           /* 0: chosen by the library; else a positive multiple of 64: targets per slice */
+  float* dist;                /* [n_query] nearest distance, or NULL */
+  int32_t* index;             /* [n_query] index of the nearest target, or NULL */
+  int n_bins;                 /* 1 .. 1024 (ignored when hist is NULL) */
+  float bin_len;              /* > 0, finite */
+  uint32_t* hist;             /* [n_bins + 2], zeroed by the call on the stream, or NULL */
+  double* stats;              /* device [6]: n_finite, sum d, sum d^2, max d, n_nonfinite, 0; or NULL */
+  void* workspace;            /* >= sr_cloud_nn_workspace(...) bytes, 16-byte aligned, stream-ordered reuse */
+  int64_t workspace_bytes;
+} sr_cloud_nn_desc;
+
+/* Bytes of workspace: the staged targets (16 per target, with or without a transform: has_xform does not
+ * change the size), the (d2, index) partial of every (slice, query) and one stats partial per query tile.
+ * With target_chunk = 0 it is a bound that never shrinks when n_query or n_target grows; it shrinks as
+ * an explicit target_chunk grows.  0 for arguments sr_cloud_nn would reject. */
+int64_t sr_cloud_nn_workspace(int64_t n_query, int64_t n_target, int target_chunk, int has_xform);
+/* Up to five launches (clear, stage targets, sweep over query tiles x target slices, merge, stats sum),
+ * asynchronous and allocation-free.  SR_EINVAL for a null desc, query, target or workspace; a count
+ * outside [1, 2^31 - 1]; all of dist, index, hist and stats NULL; with hist set, n_bins outside [1, 1024]
+ * or bin_len not positive and finite; a target_chunk that is negative, not a multiple of 64 or that cuts
+ * the targets into more than 65535 slices; a workspace that is too small or not 16-byte aligned; an fp64
+ * pointer (query_xform, target_xform, stats) that is not 8-byte aligned. */
+int sr_cloud_nn(sr_stream_t stream, const sr_cloud_nn_desc* desc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,7 @@
 //                           tests/test_debug_build.py pins the set the plain mode prints
 //   abi_host_check layout pose_eval   the same for the structs of sr_pose_pair_errors / sr_pose_align (ABI 1.9)
 //   abi_host_check layout imc_stats   the same for sr_imc_stats_desc (ABI 1.10)
+//   abi_host_check layout cloud_eval   the same for sr_cloud_nn_desc (ABI 1.11)
 //   abi_host_check check    the validation sweep; exit 0 iff every call returned what it should
 #include <cstddef>
 #include <cstdio>
@@ -152,6 +153,18 @@ void layout_imc_stats() {
           FIELD(sr_imc_stats_desc, frame_pdf), FIELD(sr_imc_stats_desc, thresh), FIELD(sr_imc_stats_desc, n_thresh),
           FIELD(sr_imc_stats_desc, pair_counts), FIELD(sr_imc_stats_desc, pair_stats),
           FIELD(sr_imc_stats_desc, workspace), FIELD(sr_imc_stats_desc, workspace_floats)));
+  std::printf("}\n");
+}
+
+void layout_cloud_eval() {
+  const char* sep = "";
+  std::printf("{");
+  STRUCT(sr_cloud_nn_desc,
+         (FIELD(sr_cloud_nn_desc, query), FIELD(sr_cloud_nn_desc, target), FIELD(sr_cloud_nn_desc, n_query),
+          FIELD(sr_cloud_nn_desc, n_target), FIELD(sr_cloud_nn_desc, query_xform), FIELD(sr_cloud_nn_desc, target_xform),
+          FIELD(sr_cloud_nn_desc, target_chunk), FIELD(sr_cloud_nn_desc, dist), FIELD(sr_cloud_nn_desc, index),
+          FIELD(sr_cloud_nn_desc, n_bins), FIELD(sr_cloud_nn_desc, bin_len), FIELD(sr_cloud_nn_desc, hist),
+          FIELD(sr_cloud_nn_desc, stats), FIELD(sr_cloud_nn_desc, workspace), FIELD(sr_cloud_nn_desc, workspace_bytes)));
   std::printf("}\n");
 }
 
@@ -567,6 +580,90 @@ void check() {
     c = ad, c.out = (double*)((char*)fake(2) + 4);
     expect("sr_pose_align out % 8", sr_pose_align(nullptr, &c), false);
   }
+  expect("sr_cloud_nn null", sr_cloud_nn(nullptr, nullptr), false);
+  {  // ABI 1.11: every rejection the header lists, then the planned shapes up to the launch
+    const int64_t nq = 8600000, nt = 8600000;
+    const int64_t need = sr_cloud_nn_workspace(nq, nt, 0, 1);
+    std::printf("cloud workspace bytes: %lld\n", (long long)need);
+    if (need < 16 * nt + 8 * nq || sr_cloud_nn_workspace(0, nt, 0, 0) != 0 || sr_cloud_nn_workspace(nq, 0, 0, 0) != 0 ||
+        sr_cloud_nn_workspace(int64_t(1) << 31, nt, 0, 0) != 0 || sr_cloud_nn_workspace(nq, int64_t(1) << 31, 0, 0) != 0 ||
+        sr_cloud_nn_workspace(nq, nt, -64, 0) != 0 || sr_cloud_nn_workspace(nq, nt, 100, 0) != 0 ||
+        sr_cloud_nn_workspace(nq, nt, 64, 0) != 0 || sr_cloud_nn_workspace(nq, nt, 0, 0) != need)
+      ++g_fail;
+    {  // the size never shrinks when a count grows, nor when an explicit chunk shrinks
+      const int64_t ns[] = {1, 63, 1024, 1025, 4096, 1 << 20, (1 << 20) + 1, 8600000, 2147483647LL};
+      for (int chunk : {0, 65536, 1 << 20})
+        for (int64_t fixed : ns) {
+          int64_t prev_q = 0, prev_t = 0;
+          for (int64_t n : ns) {
+            const int64_t wq = sr_cloud_nn_workspace(n, fixed, chunk, 0), wt = sr_cloud_nn_workspace(fixed, n, chunk, 0);
+            if (wq < prev_q || wt < prev_t || wq <= 0 || wt <= 0) ++g_fail;
+            prev_q = wq, prev_t = wt;
+          }
+        }
+      if (sr_cloud_nn_workspace(4096, 1 << 20, 128, 0) < sr_cloud_nn_workspace(4096, 1 << 20, 256, 0)) ++g_fail;
+    }
+    sr_cloud_nn_desc cd{};
+    cd.query = fake<float>(0), cd.target = fake<float>(1), cd.n_query = nq, cd.n_target = nt;
+    cd.query_xform = fake<double>(2), cd.dist = fake<float>(3), cd.index = fake<int32_t>(4), cd.n_bins = 1024;
+    cd.bin_len = 0.01f, cd.hist = fake<uint32_t>(5), cd.stats = fake<double>(6), cd.workspace = fake(7);
+    cd.workspace_bytes = need;
+    expect("sr_cloud_nn 8.6 M x 8.6 M, every output", sr_cloud_nn(nullptr, &cd), true);
+    sr_cloud_nn_desc b = cd;
+    b.n_query = 4096, b.query_xform = nullptr, b.target_xform = fake<double>(2), b.dist = nullptr, b.index = nullptr;
+    b.stats = nullptr;
+    expect("sr_cloud_nn 4096-point probe, histogram only", sr_cloud_nn(nullptr, &b), true);
+    b = cd, b.n_query = 1, b.n_target = 1, b.hist = nullptr, b.n_bins = 0, b.bin_len = 0.f, b.target_chunk = 64;
+    expect("sr_cloud_nn 1 x 1 without a histogram", sr_cloud_nn(nullptr, &b), true);
+    b = cd, b.n_query = 2147483647, b.n_target = 2147483647, b.target_chunk = 1 << 20;
+    b.workspace_bytes = sr_cloud_nn_workspace(b.n_query, b.n_target, b.target_chunk, 0);
+    expect("sr_cloud_nn 2^31 - 1 points a side", sr_cloud_nn(nullptr, &b), true);
+    b = cd, b.query = nullptr;
+    expect("sr_cloud_nn null query", sr_cloud_nn(nullptr, &b), false);
+    b = cd, b.target = nullptr;
+    expect("sr_cloud_nn null target", sr_cloud_nn(nullptr, &b), false);
+    b = cd, b.workspace = nullptr;
+    expect("sr_cloud_nn null workspace", sr_cloud_nn(nullptr, &b), false);
+    b = cd, b.n_query = 0;
+    expect("sr_cloud_nn 0 queries", sr_cloud_nn(nullptr, &b), false);
+    b = cd, b.n_query = int64_t(1) << 31;
+    expect("sr_cloud_nn 2^31 queries", sr_cloud_nn(nullptr, &b), false);
+    b = cd, b.n_target = 0;
+    expect("sr_cloud_nn 0 targets", sr_cloud_nn(nullptr, &b), false);
+    b = cd, b.n_target = int64_t(1) << 31;
+    expect("sr_cloud_nn 2^31 targets", sr_cloud_nn(nullptr, &b), false);
+    b = cd, b.dist = nullptr, b.index = nullptr, b.hist = nullptr, b.stats = nullptr;
+    expect("sr_cloud_nn every output NULL", sr_cloud_nn(nullptr, &b), false);
+    b = cd, b.n_bins = 0;
+    expect("sr_cloud_nn 0 bins", sr_cloud_nn(nullptr, &b), false);
+    b = cd, b.n_bins = 1025;
+    expect("sr_cloud_nn 1025 bins", sr_cloud_nn(nullptr, &b), false);
+    b = cd, b.bin_len = 0.f;
+    expect("sr_cloud_nn bin_len 0", sr_cloud_nn(nullptr, &b), false);
+    b = cd, b.bin_len = -1.f;
+    expect("sr_cloud_nn bin_len -1", sr_cloud_nn(nullptr, &b), false);
+    const uint32_t inf_bits = 0x7f800000u, nan_bits = 0x7fc00000u;
+    b = cd, std::memcpy(&b.bin_len, &inf_bits, sizeof(inf_bits));
+    expect("sr_cloud_nn bin_len Inf", sr_cloud_nn(nullptr, &b), false);
+    b = cd, std::memcpy(&b.bin_len, &nan_bits, sizeof(nan_bits));
+    expect("sr_cloud_nn bin_len NaN", sr_cloud_nn(nullptr, &b), false);
+    b = cd, b.target_chunk = -64;
+    expect("sr_cloud_nn target_chunk -64", sr_cloud_nn(nullptr, &b), false);
+    b = cd, b.target_chunk = 100;
+    expect("sr_cloud_nn target_chunk 100", sr_cloud_nn(nullptr, &b), false);
+    b = cd, b.target_chunk = 64, b.workspace_bytes = int64_t(1) << 62;
+    expect("sr_cloud_nn more than 65535 slices", sr_cloud_nn(nullptr, &b), false);
+    b = cd, b.workspace_bytes = need - 1;
+    expect("sr_cloud_nn workspace one byte short", sr_cloud_nn(nullptr, &b), false);
+    b = cd, b.workspace = (char*)fake(7) + 8;
+    expect("sr_cloud_nn workspace % 16", sr_cloud_nn(nullptr, &b), false);
+    b = cd, b.query_xform = (const double*)((const char*)fake(2) + 4);
+    expect("sr_cloud_nn query_xform % 8", sr_cloud_nn(nullptr, &b), false);
+    b = cd, b.target_xform = (const double*)((const char*)fake(2) + 4);
+    expect("sr_cloud_nn target_xform % 8", sr_cloud_nn(nullptr, &b), false);
+    b = cd, b.stats = (double*)((char*)fake(6) + 4);
+    expect("sr_cloud_nn stats % 8", sr_cloud_nn(nullptr, &b), false);
+  }
   expect("sr_pose_decode_f32 null", sr_pose_decode_f32(nullptr, nullptr, 9, 0, 518, 518, nullptr, nullptr), false);
   expect("sr_copy_rows_f32 null", sr_copy_rows_f32(nullptr, nullptr, 0, nullptr, 0, nullptr, 0, 0), false);
   expect("sr_conv3x3_f32 null", sr_conv3x3_f32(nullptr, nullptr, 1, 8, 8, 32, 1, 0, nullptr, 32, SR_EPI_BIAS, &ep, nullptr, 32, nullptr), false);
@@ -640,6 +737,8 @@ int main(int argc, char** argv) {
       layout_pose_eval();
     else if (argc > 2 && std::string(argv[2]) == "imc_stats")
       layout_imc_stats();
+    else if (argc > 2 && std::string(argv[2]) == "cloud_eval")
+      layout_cloud_eval();
     else
       layout();
     return 0;

@@ -167,6 +167,15 @@ class PoseAlignDesc(ctypes.Structure):
     ]
 
 
+class CloudNnDesc(ctypes.Structure):
+    """sr_cloud_nn_desc (include/sfm_amd.h)."""
+    _fields_ = [
+        ("query", _vp), ("target", _vp), ("n_query", _i64), ("n_target", _i64), ("query_xform", _vp),
+        ("target_xform", _vp), ("target_chunk", _i32), ("dist", _vp), ("index", _vp), ("n_bins", _i32),
+        ("bin_len", _f32), ("hist", _vp), ("stats", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
+    ]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "sr_last_error": (ctypes.c_char_p, []),
@@ -266,6 +275,8 @@ _PROTOS = {
     "sr_corres_sample": (_i32, [_vp, ctypes.POINTER(CorresDesc)]),
     "sr_pose_pair_errors": (_i32, [_vp, ctypes.POINTER(PosePairsDesc)]),
     "sr_pose_align": (_i32, [_vp, ctypes.POINTER(PoseAlignDesc)]),
+    "sr_cloud_nn_workspace": (_i64, [_i64, _i64, _i32, _i32]),
+    "sr_cloud_nn": (_i32, [_vp, ctypes.POINTER(CloudNnDesc)]),
 }
 EXPORTED = tuple(_PROTOS)
 

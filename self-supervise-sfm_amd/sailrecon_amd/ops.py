@@ -1401,6 +1401,62 @@ def pose_align(pred: Tensor, gt: Tensor, out: Tensor, status: Tensor, *, with_sc
     check(_lib.load().sr_pose_align(_stream(pred), ctypes.byref(d)), "sr_pose_align")
 
 
+# ---------------------------------------------------------------- scoring point clouds (utils/cloud_eval.py)
+def _cloud_points(t: Tensor, name: str) -> int:
+    """Point count of a contiguous fp32 device tensor [N, 3]."""
+    if not isinstance(t, Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous fp32 device tensor")
+    if t.dim() != 2 or t.shape[1] != 3 or not 0 < t.shape[0] < 2 ** 31:
+        raise ValueError(f"{name} must be [N, 3] with 1 <= N < 2^31, got {tuple(t.shape)}")
+    return t.shape[0]
+
+
+def cloud_nn_workspace_bytes(n_query: int, n_target: int, target_chunk: int = 0, has_xform: bool = False) -> int:
+    """sr_cloud_nn_workspace (0 for sizes or a chunk sr_cloud_nn rejects)."""
+    return int(_lib.load().sr_cloud_nn_workspace(int(n_query), int(n_target), int(target_chunk), int(bool(has_xform))))
+
+
+def cloud_nn(query: Tensor, target: Tensor, *, query_xform: Optional[Tensor] = None,
+             target_xform: Optional[Tensor] = None, dist: Optional[Tensor] = None, index: Optional[Tensor] = None,
+             hist: Optional[Tensor] = None, bin_len: float = 0.0, stats: Optional[Tensor] = None,
+             target_chunk: int = 0) -> None:
+    """sr_cloud_nn: for every query point [Nq, 3] the distance to (``dist`` [Nq] fp32) and the index of
+    (``index`` [Nq] int32) its nearest target [Nt, 3], their histogram (``hist`` [n_bins + 2], int32
+    storage of the uint32 counts, zeroed by the call; bins of ``bin_len``) and ``stats`` [6] fp64
+    (n_finite, sum d, sum d^2, max d, n_nonfinite, 0).  ``query_xform`` / ``target_xform``: fp64 device
+    tensors whose first 13 entries are scale, R row-major, t (``pose_align``'s ``out`` as it lies)."""
+    d = _lib.CloudNnDesc()
+    nq, nt = _cloud_points(query, "query"), _cloud_points(target, "target")
+    if dist is None and index is None and hist is None and stats is None:
+        raise ValueError("one of dist, index, hist and stats must be given")
+    for name, t in (("query_xform", query_xform), ("target_xform", target_xform)):
+        if t is not None and (t.dtype != torch.float64 or t.dim() != 1 or t.numel() < 13 or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous fp64 vector of at least 13 entries")
+    for name, t, dt in (("dist", dist, torch.float32), ("index", index, torch.int32)):
+        if t is not None and (t.dtype != dt or t.dim() != 1 or t.numel() != nq or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {dt} vector of {nq} entries")
+    if hist is not None:
+        if hist.dtype != torch.int32 or hist.dim() != 1 or hist.numel() < 3 or not hist.is_contiguous():
+            raise ValueError(f"hist must be a contiguous int32 [n_bins + 2] vector, got {hist.dtype} {tuple(hist.shape)}")
+        d.n_bins, d.bin_len = hist.numel() - 2, float(bin_len)
+    if stats is not None and (stats.dtype != torch.float64 or stats.numel() != 6 or not stats.is_contiguous()):
+        raise ValueError("stats must be a contiguous fp64 tensor of 6 entries")
+    for name, t in (("target", target), ("query_xform", query_xform), ("target_xform", target_xform), ("dist", dist),
+                    ("index", index), ("hist", hist), ("stats", stats)):
+        if t is not None and t.device != query.device:
+            raise ValueError(f"{name} must live on {query.device}")
+    need = cloud_nn_workspace_bytes(nq, nt, target_chunk, target_xform is not None)
+    if need <= 0:
+        raise ValueError(f"target_chunk {target_chunk} must be 0 or a positive multiple of 64 that cuts {nt} targets "
+                         "into at most 65535 slices")
+    ws = torch.empty(need, device=query.device, dtype=torch.uint8)  # stream-ordered: the caching allocator's rule
+    d.query, d.target, d.n_query, d.n_target = _p(query), _p(target), nq, nt
+    d.query_xform, d.target_xform, d.target_chunk = _p(query_xform), _p(target_xform), int(target_chunk)
+    d.dist, d.index, d.hist, d.stats = _p(dist), _p(index), _p(hist), _p(stats)
+    d.workspace, d.workspace_bytes = _p(ws), need
+    check(_lib.load().sr_cloud_nn(_stream(query), ctypes.byref(d)), "sr_cloud_nn")
+
+
 # ---------------------------------------------------------------- training step (SURVEY §8(f) rank 4)
 _TRAIN_WS = {}  # ((device, stream), name) -> fp32 workspace
 

@@ -920,6 +920,60 @@ def attn_rows():
               f"({ops.last_kernel()})")
 
 
+def cloud(runs=3):
+    """Nearest-neighbour sweep of the point-cloud scores (sr_cloud_nn: every output) against a chunked
+    ``torch.cdist(q, t).min(1)`` (its distance matrix in chunks of at most 2 GiB), in alternation in one
+    process, ``runs`` timed runs each after one warm-up, HIP events.  Shapes: 2^20 x 2^20 and 2^18 x 8.6 M
+    (a probe against a 32-view scene at 518 px).  Per shape: pairs/s, and the fraction of the fp32 VALU
+    rate with the inner loop counted as 9 operations per pair (3 subtractions, a multiply, 2 FMAs, a
+    minimum, a compare and a select, an FMA counted once): plain = 256 CUs x 4 SIMDs x 32 lanes x 2.4 GHz
+    = 78.6 T op/s (MI355X_MICROARCH: a wave64 VALU instruction issues in 2 cycles), packed = twice that,
+    every operation a two-wide v_pk_*.  Then the largest dist difference between the two on a cloud 1e3
+    from the origin with 1e-3 between neighbours."""
+    plain = 256 * 4 * 32 * 2.4e9
+    g = torch.Generator(device=DEV).manual_seed(0)
+
+    def kernel(q, t):
+        dist = torch.empty(q.shape[0], device=DEV, dtype=torch.float32)
+        index = torch.empty(q.shape[0], device=DEV, dtype=torch.int32)
+        hist = torch.empty(1026, device=DEV, dtype=torch.int32)
+        stats = torch.empty(6, device=DEV, dtype=torch.float64)
+        ops.cloud_nn(q, t, dist=dist, index=index, hist=hist, bin_len=0.001, stats=stats)
+        return dist
+
+    def baseline(q, t):
+        rows = max(1, (1 << 29) // t.shape[0])
+        return torch.cat([torch.cdist(q[a:a + rows], t).min(1).values for a in range(0, q.shape[0], rows)])
+
+    for nq, nt in ((1 << 20, 1 << 20), (1 << 18, 8_600_000)):
+        q = torch.rand(nq, 3, device=DEV, generator=g) * 2 - 1
+        t = torch.rand(nt, 3, device=DEV, generator=g) * 2 - 1
+        times = {"sr_cloud_nn": [], "cdist+min": []}
+        fns = {"sr_cloud_nn": kernel, "cdist+min": baseline}
+        for name, fn in fns.items():
+            fn(q, t)
+        torch.cuda.synchronize()
+        for _ in range(runs):
+            for name, fn in fns.items():
+                times[name].append(timeit(lambda: fn(q, t), reps=1, warm=0))
+        diff = float((kernel(q, t) - baseline(q, t)).abs().max())
+        for name, ms in times.items():
+            best, rate = min(ms), nq * nt / (min(ms) * 1e-3)
+            print(f"cloud {nq} x {nt} {name:11s}: " + " ".join(f"{m:9.2f}" for m in ms) + f" ms  best {best:9.2f} ms  "
+                  f"{rate / 1e12:6.3f} T pairs/s  {9 * rate / plain:6.1%} of the plain, {9 * rate / (2 * plain):6.1%} of the "
+                  f"packed fp32 VALU rate", flush=True)
+        print(f"cloud {nq} x {nt}: sr_cloud_nn is {min(times['cdist+min']) / min(times['sr_cloud_nn']):.2f} x the baseline's "
+              f"speed; largest dist difference {diff:.3e}  [{ops.last_kernel()}]", flush=True)
+        del q, t
+    q = 1e3 + 1e-3 * 11 * torch.rand(4096, 3, device=DEV, generator=g)
+    t = 1e3 + 1e-3 * 11 * torch.rand(65536, 3, device=DEV, generator=g)
+    ref = torch.cat([torch.cdist(q[a:a + 256].double(), t.double()).min(1).values for a in range(0, 4096, 256)])
+    print(f"cloud far (1e3 + 1e-3 U(0, 11), 4096 x 65536; fp64 distances up to {float(ref.max()):.3e}): largest dist "
+          f"difference sr_cloud_nn - cdist+min {float((kernel(q, t) - baseline(q, t)).abs().max()):.3e}; against fp64: "
+          f"sr_cloud_nn {float((kernel(q, t).double() - ref).abs().max()):.3e}, cdist+min "
+          f"{float((baseline(q, t).double() - ref).abs().max()):.3e}", flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["attn", "gemm", "ln"]
     for w in which:
