@@ -1086,6 +1086,118 @@ int64_t sr_cloud_nn_workspace(int64_t n_query, int64_t n_target, int target_chun
  * pointer (query_xform, target_xform, stats) that is not 8-byte aligned. */
 int sr_cloud_nn(sr_stream_t stream, const sr_cloud_nn_desc* desc);
 
+/* ------------------------------------------------------------------------------------------
+ * Exact order statistics by group (ABI 1.12): a grid-wide radix select on the fp32 bit patterns.
+ * Definitions: DESIGN.md "Scoring depth maps", csrc/sr_depth_eval.hip.
+ *   considered  an element of x[r][0 .. row_len) whose mask byte (if a mask is given) is non-zero and
+ *               whose exponent bits are not all ones (finite: a test on the bits).  Every other element
+ *               of the row counts as skipped.  Elements at row_len .. row_stride are never loaded.
+ *   order       that of the key bits ^ (sign ? 0xffffffff : 0x80000000), unsigned: the usual order of
+ *               the reals with -0 before +0
+ *   rank        with the n considered values of a group ascending s[0 .. n - 1], the fraction num / den
+ *               selects s[max((num n + den - 1) / den - 1, 0)] in 64-bit integers: 1 / 2 is the lower
+ *               median s[(n - 1) / 2], 9 / 10 is s[(9 n + 9) / 10 - 1], 0 the minimum, 1 the maximum
+ *   value       the selected element, by its bits; 0x7fc00000 (a quiet NaN) for a group with n = 0
+ *   Four passes over the rows, one per 8-bit digit, all ranks at once: LDS histograms per workgroup,
+ *   flushed with integer atomics; a group's prefix and remaining rank advance on the device between
+ *   passes.  Integer counts only: any two runs and any blocks_per_row give the same bits.
+ *   A row whose group index lies outside [0, n_groups) is ignored (nothing is indexed through it).
+ * ------------------------------------------------------------------------------------------ */
+#define SR_SELECT_MAX_RANKS 4
+typedef struct sr_select_desc {
+  const float* x;             /* [n_rows][row_stride] fp32 */
+  const uint8_t* mask;        /* [n_rows][row_stride] bytes, 0 = skip, or NULL */
+  const int32_t* group;       /* [n_rows] in [0, n_groups), or NULL: row r is group r (n_groups == n_rows) */
+  int64_t n_rows, row_len, row_stride; /* n_rows * row_len <= 2^31 */
+  int n_groups;               /* 1 .. n_rows */
+  int n_ranks;                /* 1 .. SR_SELECT_MAX_RANKS */
+  int32_t rank_num[SR_SELECT_MAX_RANKS]; /* 0 <= num <= den */
+  int32_t rank_den[SR_SELECT_MAX_RANKS]; /* 1 <= den <= 2^20 */
+  int blocks_per_row;         /* 0: chosen by the library; else 1 .. 65535 workgroups per row */
+  float* value;               /* [n_groups][n_ranks] */
+  uint32_t* count;            /* [n_groups][2]: considered, skipped; or NULL */
+  void* workspace;            /* >= sr_select_workspace(n_groups, n_ranks) bytes, 16-byte aligned, stream-ordered reuse */
+  int64_t workspace_bytes;
+} sr_select_desc;
+
+/* Bytes of workspace: the [n_groups][n_ranks][256] counters, each (group, rank)'s prefix and remaining
+ * rank, each group's two counts.  Never shrinks when a count grows; 0 for arguments outside the ranges. */
+int64_t sr_select_workspace(int n_groups, int n_ranks);
+/* One clearing node and eight launches (per digit: histogram, then one workgroup per group advancing
+ * the prefixes), asynchronous and allocation-free.  SR_EINVAL for a null desc, x, value or workspace;
+ * n_ranks outside [1, 4]; a fraction with num < 0, den < 1, num > den or den > 2^20; n_rows or row_len
+ * below 1; row_stride < row_len; n_rows * row_len above 2^31; n_groups outside [1, n_rows]; a NULL
+ * group with n_groups != n_rows; blocks_per_row outside [0, 65535] or n_rows * blocks_per_row above
+ * 2^31 - 1; a workspace that is too small or not 16-byte aligned. */
+int sr_select_ranks(sr_stream_t stream, const sr_select_desc* desc);
+
+/* ------------------------------------------------------------------------------------------
+ * Scoring depth maps (ABI 1.12): a predicted depth map against a reference one, per group of views,
+ * after an alignment of the prediction; the sums, counts and histogram that AbsRel, SqRel, RMSE,
+ * RMSE-log, SILog, log10, delta < 1.25^k and inlier fractions are read off on the host.
+ * Definitions: DESIGN.md "Scoring depth maps", csrc/sr_depth_eval.hip.
+ *   valid      mask byte non-zero, conf >= conf_min[view] (a NaN conf is invalid), gt finite with
+ *              gt_min < gt <= gt_max, pred finite (tests on the bits).  Every other pixel counts in
+ *              n_invalid and nowhere else.
+ *   alignment  per group, over its valid pixels; xform[g] = (s, t) in fp64, status[g] bits:
+ *              NONE (1, 0); MEDIAN s = (double)med(gt) / (double)med(pred), lower medians by
+ *              sr_select_ranks' rule (med(pred) <= 0: bit 0, s = 1); SCALE s = sum g p / sum p p
+ *              (sum p p = 0: bit 0, s = 1); SCALE_SHIFT the least-squares fit of s p + t to g in the
+ *              centred two-pass form, s = sum (p - pm)(g - gm) / sum (p - pm)^2, t = gm - s pm
+ *              (sum (p - pm)^2 = 0: bit 0, s = 1, t = gm - pm); GIVEN (s, t) read from xform, which
+ *              is left as it is.  Bit 1: the group has no valid pixel; (1, 0) and every sum is zero.
+ *   per pixel  a = fl32(s p + t), product and sum in fp64, not contracted, rounded once.  In fp64 from
+ *              the fp32 a and g: rel = |a - g| / g, (a - g)^2, (a - g)^2 / g; for a > 0 and finite
+ *              d = ln a - ln g, d^2, |d| / ln 10; else the pixel counts in n_nonpos, is left out of
+ *              the three log sums and fails every delta.  delta_k: a < c g and g < c a, c = 1.25^k.
+ *   stats      [16] fp64 per row: n_valid, n_nonpos, n_invalid, sum rel, sum (a - g)^2 / g,
+ *              sum (a - g)^2, sum d, sum d^2, sum |d| / ln 10, delta_1, delta_2, delta_3 counts,
+ *              max rel, 0, 0, 0.  A lane's pixels ascending, a fixed LDS tree, one partial per
+ *              workgroup, the partials of a group summed in ascending order by a fixed tree.
+ *   hist       of r32 = fl32(rel): slot k < n_bins counts k <= fl32(r32 / bin_len) < k + 1, slot n_bins
+ *              the larger values, slot n_bins + 1 the non-finite r32.  Integer atomics only.
+ *   rows       row n_groups of stats, hist and rel_q pools all groups, each under its own alignment:
+ *              stats and hist summed from the group rows in ascending order, rel_q by one more select
+ * ------------------------------------------------------------------------------------------ */
+enum sr_depth_align { SR_DEPTH_ALIGN_NONE = 0, SR_DEPTH_ALIGN_MEDIAN = 1, SR_DEPTH_ALIGN_SCALE = 2,
+                      SR_DEPTH_ALIGN_SCALE_SHIFT = 3, SR_DEPTH_ALIGN_GIVEN = 4 };
+typedef struct sr_depth_eval_desc {
+  const float* pred;          /* [n_views][stride] fp32 */
+  const float* gt;            /* [n_views][stride] fp32 */
+  const uint8_t* mask;        /* [n_views][stride] bytes, or NULL */
+  const float* conf;          /* [n_views][stride] fp32, or NULL; goes with conf_min */
+  const float* conf_min;      /* device [n_views], or NULL */
+  const int32_t* group;       /* [n_views] in [0, n_groups), or NULL: view v is group v (n_groups == n_views) */
+  int64_t n_pix, stride;      /* pixels used per view, floats between views; n_views * stride <= 2^31 */
+  int n_views;                /* 1 .. 65535 */
+  int n_groups;               /* 1 .. n_views */
+  float gt_min, gt_max;       /* gt_min < gt_max, neither a NaN; 0 and +Inf make zeros invalid */
+  int align;                  /* sr_depth_align */
+  int n_bins;                 /* 1 .. 1024 */
+  float bin_len;              /* > 0, finite */
+  double* xform;              /* [n_groups][2] (s, t): written, or read under SR_DEPTH_ALIGN_GIVEN */
+  int32_t* status;            /* [n_groups] */
+  double* stats;              /* [n_groups + 1][16] */
+  uint32_t* hist;             /* [n_groups + 1][n_bins + 2]; zeroed by the call, on the stream */
+  float* aligned;             /* [n_views][n_pix] a, quiet NaN bits on invalid pixels, or NULL */
+  float* rel_err;             /* [n_views][n_pix] r32, quiet NaN bits on invalid pixels, or NULL */
+  float* rel_q;               /* [n_groups + 1][2] exact median and p90 of the finite r32, or NULL */
+  void* workspace;            /* >= sr_depth_eval_workspace(...) bytes, 16-byte aligned, stream-ordered reuse */
+  int64_t workspace_bytes;
+} sr_depth_eval_desc;
+
+/* Bytes of workspace: the validity bytes, the per-workgroup partial sums, the select's counters and, with
+ * rel_q_scratch (rel_q wanted without rel_err), one float per pixel.  Never shrinks when n_views, n_pix,
+ * stride or n_groups grows; 0 for arguments sr_depth_eval would reject. */
+int64_t sr_depth_eval_workspace(int n_views, int64_t n_pix, int64_t stride, int n_groups, int rel_q_scratch);
+/* Asynchronous and allocation-free.  SR_EINVAL for a null desc, pred, gt, xform, status, stats, hist or
+ * workspace; n_views outside [1, 65535]; n_pix < 1; stride < n_pix; n_views * stride above 2^31; n_groups
+ * outside [1, n_views]; a NULL group with n_groups != n_views; exactly one of conf and conf_min; gt_min or
+ * gt_max a NaN, or gt_min >= gt_max; align outside sr_depth_align; n_bins outside [1, 1024]; bin_len not
+ * positive and finite; a workspace that is too small or not 16-byte aligned; an fp64 pointer (xform, stats)
+ * that is not 8-byte aligned. */
+int sr_depth_eval(sr_stream_t stream, const sr_depth_eval_desc* desc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@
 //   abi_host_check layout pose_eval   the same for the structs of sr_pose_pair_errors / sr_pose_align (ABI 1.9)
 //   abi_host_check layout imc_stats   the same for sr_imc_stats_desc (ABI 1.10)
 //   abi_host_check layout cloud_eval   the same for sr_cloud_nn_desc (ABI 1.11)
+//   abi_host_check layout depth_eval   the same for sr_select_desc and sr_depth_eval_desc (ABI 1.12)
 //   abi_host_check check    the validation sweep; exit 0 iff every call returned what it should
 #include <cstddef>
 #include <cstdio>
@@ -165,6 +166,27 @@ void layout_cloud_eval() {
           FIELD(sr_cloud_nn_desc, target_chunk), FIELD(sr_cloud_nn_desc, dist), FIELD(sr_cloud_nn_desc, index),
           FIELD(sr_cloud_nn_desc, n_bins), FIELD(sr_cloud_nn_desc, bin_len), FIELD(sr_cloud_nn_desc, hist),
           FIELD(sr_cloud_nn_desc, stats), FIELD(sr_cloud_nn_desc, workspace), FIELD(sr_cloud_nn_desc, workspace_bytes)));
+  std::printf("}\n");
+}
+
+void layout_depth_eval() {
+  const char* sep = "";
+  std::printf("{");
+  STRUCT(sr_select_desc,
+         (FIELD(sr_select_desc, x), FIELD(sr_select_desc, mask), FIELD(sr_select_desc, group), FIELD(sr_select_desc, n_rows),
+          FIELD(sr_select_desc, row_len), FIELD(sr_select_desc, row_stride), FIELD(sr_select_desc, n_groups),
+          FIELD(sr_select_desc, n_ranks), FIELD(sr_select_desc, rank_num), FIELD(sr_select_desc, rank_den),
+          FIELD(sr_select_desc, blocks_per_row), FIELD(sr_select_desc, value), FIELD(sr_select_desc, count),
+          FIELD(sr_select_desc, workspace), FIELD(sr_select_desc, workspace_bytes)));
+  STRUCT(sr_depth_eval_desc,
+         (FIELD(sr_depth_eval_desc, pred), FIELD(sr_depth_eval_desc, gt), FIELD(sr_depth_eval_desc, mask),
+          FIELD(sr_depth_eval_desc, conf), FIELD(sr_depth_eval_desc, conf_min), FIELD(sr_depth_eval_desc, group),
+          FIELD(sr_depth_eval_desc, n_pix), FIELD(sr_depth_eval_desc, stride), FIELD(sr_depth_eval_desc, n_views),
+          FIELD(sr_depth_eval_desc, n_groups), FIELD(sr_depth_eval_desc, gt_min), FIELD(sr_depth_eval_desc, gt_max),
+          FIELD(sr_depth_eval_desc, align), FIELD(sr_depth_eval_desc, n_bins), FIELD(sr_depth_eval_desc, bin_len),
+          FIELD(sr_depth_eval_desc, xform), FIELD(sr_depth_eval_desc, status), FIELD(sr_depth_eval_desc, stats),
+          FIELD(sr_depth_eval_desc, hist), FIELD(sr_depth_eval_desc, aligned), FIELD(sr_depth_eval_desc, rel_err),
+          FIELD(sr_depth_eval_desc, rel_q), FIELD(sr_depth_eval_desc, workspace), FIELD(sr_depth_eval_desc, workspace_bytes)));
   std::printf("}\n");
 }
 
@@ -664,6 +686,209 @@ void check() {
     b = cd, b.stats = (double*)((char*)fake(6) + 4);
     expect("sr_cloud_nn stats % 8", sr_cloud_nn(nullptr, &b), false);
   }
+  expect("sr_select_ranks null", sr_select_ranks(nullptr, nullptr), false);
+  expect("sr_depth_eval null", sr_depth_eval(nullptr, nullptr), false);
+  {  // ABI 1.12: every rejection the header lists, then the planned shapes up to the launch
+    const int64_t pix = 518 * 518;
+    const int64_t need = sr_select_workspace(64, 2);
+    std::printf("select workspace bytes: %lld\n", (long long)need);
+    if (need < 64 * 2 * 256 * 4 || sr_select_workspace(0, 1) != 0 || sr_select_workspace(1, 0) != 0 ||
+        sr_select_workspace(1, 5) != 0 || sr_select_workspace(-1, 1) != 0)
+      ++g_fail;
+    {  // never shrinks when a count grows
+      int64_t prev_g = 0;
+      for (int g : {1, 2, 63, 64, 65, 4096, 65535, 1 << 20, 2147483647}) {
+        int64_t prev_r = 0;
+        for (int r = 1; r <= SR_SELECT_MAX_RANKS; ++r) {
+          const int64_t w = sr_select_workspace(g, r);
+          if (w <= 0 || w < prev_r || (w & 15)) ++g_fail;
+          prev_r = w;
+        }
+        if (sr_select_workspace(g, 1) < prev_g) ++g_fail;
+        prev_g = sr_select_workspace(g, 1);
+      }
+    }
+    sr_select_desc sd{};
+    sd.x = fake<float>(0), sd.mask = fake<uint8_t>(1), sd.group = fake<int32_t>(2), sd.n_rows = 64, sd.row_len = pix;
+    sd.row_stride = pix, sd.n_groups = 64, sd.n_ranks = 2, sd.rank_num[0] = 1, sd.rank_den[0] = 2, sd.rank_num[1] = 9;
+    sd.rank_den[1] = 10, sd.value = fake<float>(3), sd.count = fake<uint32_t>(4), sd.workspace = fake(5);
+    sd.workspace_bytes = need;
+    expect("sr_select_ranks 64 x 518 x 518, two ranks", sr_select_ranks(nullptr, &sd), true);
+    sr_select_desc b = sd;
+    b.mask = nullptr, b.group = nullptr, b.count = nullptr, b.blocks_per_row = 7;
+    expect("sr_select_ranks bare, 7 workgroups a row", sr_select_ranks(nullptr, &b), true);
+    b = sd, b.n_rows = 1, b.row_len = int64_t(1) << 31, b.row_stride = b.row_len, b.n_groups = 1, b.n_ranks = 4;
+    b.rank_num[2] = 0, b.rank_den[2] = 1, b.rank_num[3] = 1 << 20, b.rank_den[3] = 1 << 20;
+    b.workspace_bytes = sr_select_workspace(1, 4);
+    expect("sr_select_ranks one row of 2^31, four ranks", sr_select_ranks(nullptr, &b), true);
+    b = sd, b.n_rows = 1, b.row_len = 1, b.row_stride = 1, b.n_groups = 1;
+    expect("sr_select_ranks 1 x 1", sr_select_ranks(nullptr, &b), true);
+    b = sd, b.n_groups = 1, b.row_stride = pix + 3;
+    expect("sr_select_ranks one group, padded rows", sr_select_ranks(nullptr, &b), true);
+    b = sd, b.x = nullptr;
+    expect("sr_select_ranks null x", sr_select_ranks(nullptr, &b), false);
+    b = sd, b.value = nullptr;
+    expect("sr_select_ranks null value", sr_select_ranks(nullptr, &b), false);
+    b = sd, b.workspace = nullptr;
+    expect("sr_select_ranks null workspace", sr_select_ranks(nullptr, &b), false);
+    b = sd, b.n_ranks = 0;
+    expect("sr_select_ranks 0 ranks", sr_select_ranks(nullptr, &b), false);
+    b = sd, b.n_ranks = 5;
+    expect("sr_select_ranks 5 ranks", sr_select_ranks(nullptr, &b), false);
+    b = sd, b.rank_num[1] = -1;
+    expect("sr_select_ranks num -1", sr_select_ranks(nullptr, &b), false);
+    b = sd, b.rank_den[1] = 0;
+    expect("sr_select_ranks den 0", sr_select_ranks(nullptr, &b), false);
+    b = sd, b.rank_num[0] = 3;
+    expect("sr_select_ranks num > den", sr_select_ranks(nullptr, &b), false);
+    b = sd, b.rank_den[0] = (1 << 20) + 1;
+    expect("sr_select_ranks den 2^20 + 1", sr_select_ranks(nullptr, &b), false);
+    b = sd, b.n_rows = 0;
+    expect("sr_select_ranks 0 rows", sr_select_ranks(nullptr, &b), false);
+    b = sd, b.row_len = 0;
+    expect("sr_select_ranks row_len 0", sr_select_ranks(nullptr, &b), false);
+    b = sd, b.row_stride = pix - 1;
+    expect("sr_select_ranks stride < row_len", sr_select_ranks(nullptr, &b), false);
+    b = sd, b.n_rows = 8192, b.n_groups = 64;  // 8192 x 268,324 > 2^31
+    expect("sr_select_ranks more than 2^31 elements", sr_select_ranks(nullptr, &b), false);
+    b = sd, b.n_groups = 0;
+    expect("sr_select_ranks 0 groups", sr_select_ranks(nullptr, &b), false);
+    b = sd, b.n_groups = 65, b.workspace_bytes = int64_t(1) << 40;
+    expect("sr_select_ranks more groups than rows", sr_select_ranks(nullptr, &b), false);
+    b = sd, b.group = nullptr, b.n_groups = 3;
+    expect("sr_select_ranks no group, 3 groups", sr_select_ranks(nullptr, &b), false);
+    b = sd, b.blocks_per_row = -1;
+    expect("sr_select_ranks blocks_per_row -1", sr_select_ranks(nullptr, &b), false);
+    b = sd, b.blocks_per_row = 65536;
+    expect("sr_select_ranks blocks_per_row 65536", sr_select_ranks(nullptr, &b), false);
+    b = sd, b.n_rows = 1 << 20, b.row_len = 1, b.row_stride = 1, b.n_groups = 1, b.blocks_per_row = 4096;
+    expect("sr_select_ranks 2^32 workgroups", sr_select_ranks(nullptr, &b), false);
+    b = sd, b.workspace_bytes = need - 1;
+    expect("sr_select_ranks workspace one byte short", sr_select_ranks(nullptr, &b), false);
+    b = sd, b.workspace = (char*)fake(5) + 8;
+    expect("sr_select_ranks workspace % 16", sr_select_ranks(nullptr, &b), false);
+
+    const int64_t dneed = sr_depth_eval_workspace(64, pix, pix, 64, 1);
+    std::printf("depth workspace bytes: %lld\n", (long long)dneed);
+    if (dneed < 64 * pix * 5 || sr_depth_eval_workspace(64, pix, pix, 64, 0) > dneed - 64 * pix * 4 ||
+        sr_depth_eval_workspace(0, pix, pix, 1, 0) != 0 || sr_depth_eval_workspace(65536, 1, 1, 1, 0) != 0 ||
+        sr_depth_eval_workspace(64, 0, pix, 64, 0) != 0 || sr_depth_eval_workspace(64, pix, pix - 1, 64, 0) != 0 ||
+        sr_depth_eval_workspace(64, pix, pix, 0, 0) != 0 || sr_depth_eval_workspace(64, pix, pix, 65, 0) != 0 ||
+        sr_depth_eval_workspace(8192, pix, pix, 1, 0) != 0)
+      ++g_fail;
+    {  // never shrinks when a count grows
+      const int64_t ps[] = {1, 2047, 2048, 2049, 4900, pix, pix + 1, 1 << 20};
+      const int vs[] = {1, 2, 5, 64, 65, 2000};
+      for (int scratch : {0, 1}) {
+        for (int64_t n : ps) {
+          int64_t prev = 0;
+          for (int v : vs) {
+            const int64_t w = sr_depth_eval_workspace(v, n, n, 1, scratch), wg = sr_depth_eval_workspace(v, n, n, v, scratch);
+            if (w <= 0 || w < prev || wg < w || sr_depth_eval_workspace(v, n, n + 5, 1, scratch) < w) ++g_fail;
+            prev = w;
+          }
+        }
+        for (int v : vs) {
+          int64_t prev = 0;
+          for (int64_t n : ps) {
+            const int64_t w = sr_depth_eval_workspace(v, n, 1 << 20, 1, scratch);
+            if (w <= 0 || w < prev) ++g_fail;
+            prev = w;
+          }
+        }
+      }
+    }
+    sr_depth_eval_desc dd{};
+    dd.pred = fake<float>(0), dd.gt = fake<float>(1), dd.mask = fake<uint8_t>(2), dd.conf = fake<float>(3);
+    dd.conf_min = fake<float>(4), dd.group = fake<int32_t>(5), dd.n_pix = pix, dd.stride = pix, dd.n_views = 64;
+    dd.n_groups = 64, dd.gt_min = 0.f, dd.gt_max = 1e30f, dd.align = SR_DEPTH_ALIGN_MEDIAN, dd.n_bins = 1024;
+    dd.bin_len = 0.005f, dd.xform = fake<double>(6), dd.status = fake<int32_t>(7), dd.stats = fake<double>(8);
+    dd.hist = fake<uint32_t>(9), dd.aligned = fake<float>(10), dd.rel_err = fake<float>(11), dd.rel_q = fake<float>(12);
+    dd.workspace = fake(13), dd.workspace_bytes = dneed;
+    expect("sr_depth_eval 64 x 518 x 518 MEDIAN, every output", sr_depth_eval(nullptr, &dd), true);
+    sr_depth_eval_desc c = dd;
+    for (int align : {SR_DEPTH_ALIGN_NONE, SR_DEPTH_ALIGN_SCALE, SR_DEPTH_ALIGN_SCALE_SHIFT, SR_DEPTH_ALIGN_GIVEN}) {
+      c = dd, c.align = align, c.n_views = 5, c.n_groups = 2;
+      expect("sr_depth_eval 5 views in 2 groups", sr_depth_eval(nullptr, &c), true);
+    }
+    c = dd, c.mask = nullptr, c.conf = nullptr, c.conf_min = nullptr, c.group = nullptr, c.aligned = nullptr;
+    c.rel_err = nullptr;
+    expect("sr_depth_eval bare, rel_q through the scratch", sr_depth_eval(nullptr, &c), true);
+    c.rel_q = nullptr, c.workspace_bytes = sr_depth_eval_workspace(64, pix, pix, 64, 0);
+    expect("sr_depth_eval bare, no quantiles", sr_depth_eval(nullptr, &c), true);
+    c = dd, c.n_views = 1, c.n_groups = 1, c.n_pix = 1, c.stride = 1, c.n_bins = 1;
+    expect("sr_depth_eval 1 x 1", sr_depth_eval(nullptr, &c), true);
+    const uint32_t inf_bits = 0x7f800000u, nan_bits = 0x7fc00000u;
+    c = dd, std::memcpy(&c.gt_max, &inf_bits, sizeof(inf_bits));
+    expect("sr_depth_eval gt_max Inf", sr_depth_eval(nullptr, &c), true);
+    c = dd, c.pred = nullptr;
+    expect("sr_depth_eval null pred", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.gt = nullptr;
+    expect("sr_depth_eval null gt", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.xform = nullptr;
+    expect("sr_depth_eval null xform", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.status = nullptr;
+    expect("sr_depth_eval null status", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.stats = nullptr;
+    expect("sr_depth_eval null stats", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.hist = nullptr;
+    expect("sr_depth_eval null hist", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.workspace = nullptr;
+    expect("sr_depth_eval null workspace", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.n_views = 0;
+    expect("sr_depth_eval 0 views", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.n_views = 65536, c.n_pix = 1, c.stride = 1;
+    expect("sr_depth_eval 65536 views", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.n_pix = 0;
+    expect("sr_depth_eval 0 pixels", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.stride = pix - 1;
+    expect("sr_depth_eval stride < n_pix", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.n_views = 8192, c.workspace_bytes = int64_t(1) << 50;
+    expect("sr_depth_eval more than 2^31 floats", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.n_groups = 0;
+    expect("sr_depth_eval 0 groups", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.n_groups = 65, c.workspace_bytes = int64_t(1) << 50;
+    expect("sr_depth_eval more groups than views", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.group = nullptr, c.n_groups = 1;
+    expect("sr_depth_eval no group, 1 group", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.conf_min = nullptr;
+    expect("sr_depth_eval conf without conf_min", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.conf = nullptr;
+    expect("sr_depth_eval conf_min without conf", sr_depth_eval(nullptr, &c), false);
+    c = dd, std::memcpy(&c.gt_min, &nan_bits, sizeof(nan_bits));
+    expect("sr_depth_eval gt_min NaN", sr_depth_eval(nullptr, &c), false);
+    c = dd, std::memcpy(&c.gt_max, &nan_bits, sizeof(nan_bits));
+    expect("sr_depth_eval gt_max NaN", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.gt_min = 2.f, c.gt_max = 2.f;
+    expect("sr_depth_eval gt_min == gt_max", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.align = -1;
+    expect("sr_depth_eval align -1", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.align = 5;
+    expect("sr_depth_eval align 5", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.n_bins = 0;
+    expect("sr_depth_eval 0 bins", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.n_bins = 1025;
+    expect("sr_depth_eval 1025 bins", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.bin_len = 0.f;
+    expect("sr_depth_eval bin_len 0", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.bin_len = -1.f;
+    expect("sr_depth_eval bin_len -1", sr_depth_eval(nullptr, &c), false);
+    c = dd, std::memcpy(&c.bin_len, &inf_bits, sizeof(inf_bits));
+    expect("sr_depth_eval bin_len Inf", sr_depth_eval(nullptr, &c), false);
+    c = dd, std::memcpy(&c.bin_len, &nan_bits, sizeof(nan_bits));
+    expect("sr_depth_eval bin_len NaN", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.workspace_bytes = dneed - 64 * pix * 4;
+    c.rel_err = nullptr;
+    expect("sr_depth_eval workspace without the scratch", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.workspace_bytes = sr_depth_eval_workspace(64, pix, pix, 64, 0) - 1;
+    expect("sr_depth_eval workspace one byte short", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.workspace = (char*)fake(13) + 8;
+    expect("sr_depth_eval workspace % 16", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.xform = (double*)((char*)fake(6) + 4);
+    expect("sr_depth_eval xform % 8", sr_depth_eval(nullptr, &c), false);
+    c = dd, c.stats = (double*)((char*)fake(8) + 4);
+    expect("sr_depth_eval stats % 8", sr_depth_eval(nullptr, &c), false);
+  }
   expect("sr_pose_decode_f32 null", sr_pose_decode_f32(nullptr, nullptr, 9, 0, 518, 518, nullptr, nullptr), false);
   expect("sr_copy_rows_f32 null", sr_copy_rows_f32(nullptr, nullptr, 0, nullptr, 0, nullptr, 0, 0), false);
   expect("sr_conv3x3_f32 null", sr_conv3x3_f32(nullptr, nullptr, 1, 8, 8, 32, 1, 0, nullptr, 32, SR_EPI_BIAS, &ep, nullptr, 32, nullptr), false);
@@ -739,6 +964,8 @@ int main(int argc, char** argv) {
       layout_imc_stats();
     else if (argc > 2 && std::string(argv[2]) == "cloud_eval")
       layout_cloud_eval();
+    else if (argc > 2 && std::string(argv[2]) == "depth_eval")
+      layout_depth_eval();
     else
       layout();
     return 0;

@@ -176,6 +176,25 @@ class CloudNnDesc(ctypes.Structure):
     ]
 
 
+class SelectDesc(ctypes.Structure):
+    """sr_select_desc (include/sfm_amd.h)."""
+    _fields_ = [
+        ("x", _vp), ("mask", _vp), ("group", _vp), ("n_rows", _i64), ("row_len", _i64), ("row_stride", _i64),
+        ("n_groups", _i32), ("n_ranks", _i32), ("rank_num", _i32 * 4), ("rank_den", _i32 * 4), ("blocks_per_row", _i32),
+        ("value", _vp), ("count", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
+    ]
+
+
+class DepthEvalDesc(ctypes.Structure):
+    """sr_depth_eval_desc (include/sfm_amd.h)."""
+    _fields_ = [
+        ("pred", _vp), ("gt", _vp), ("mask", _vp), ("conf", _vp), ("conf_min", _vp), ("group", _vp),
+        ("n_pix", _i64), ("stride", _i64), ("n_views", _i32), ("n_groups", _i32), ("gt_min", _f32), ("gt_max", _f32),
+        ("align", _i32), ("n_bins", _i32), ("bin_len", _f32), ("xform", _vp), ("status", _vp), ("stats", _vp),
+        ("hist", _vp), ("aligned", _vp), ("rel_err", _vp), ("rel_q", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
+    ]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "sr_last_error": (ctypes.c_char_p, []),
@@ -277,6 +296,10 @@ _PROTOS = {
     "sr_pose_align": (_i32, [_vp, ctypes.POINTER(PoseAlignDesc)]),
     "sr_cloud_nn_workspace": (_i64, [_i64, _i64, _i32, _i32]),
     "sr_cloud_nn": (_i32, [_vp, ctypes.POINTER(CloudNnDesc)]),
+    "sr_select_workspace": (_i64, [_i32, _i32]),
+    "sr_select_ranks": (_i32, [_vp, ctypes.POINTER(SelectDesc)]),
+    "sr_depth_eval_workspace": (_i64, [_i32, _i64, _i64, _i32, _i32]),
+    "sr_depth_eval": (_i32, [_vp, ctypes.POINTER(DepthEvalDesc)]),
 }
 EXPORTED = tuple(_PROTOS)
 

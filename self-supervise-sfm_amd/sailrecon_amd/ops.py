@@ -1457,6 +1457,124 @@ def cloud_nn(query: Tensor, target: Tensor, *, query_xform: Optional[Tensor] = N
     check(_lib.load().sr_cloud_nn(_stream(query), ctypes.byref(d)), "sr_cloud_nn")
 
 
+# ---------------------------------------------------------------- order statistics, scoring depth maps (utils/depth_eval.py)
+DEPTH_ALIGN = {"none": 0, "median": 1, "scale": 2, "scale_shift": 3, "given": 4}
+
+
+def _rows(t: Tensor, name: str, dtype) -> Tuple[int, int, int]:
+    """(rows, row length, row stride) of a 2-D device tensor whose rows are contiguous."""
+    if not isinstance(t, Tensor) or not t.is_cuda or t.dtype != dtype:
+        raise ValueError(f"{name} must be a {dtype} device tensor")
+    if t.dim() != 2 or t.shape[0] == 0 or t.shape[1] == 0 or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        raise ValueError(f"{name} must be [rows, length] with contiguous rows, got {tuple(t.shape)} strides {t.stride()}")
+    return t.shape[0], t.shape[1], t.stride(0)
+
+
+def _like_rows(t: Optional[Tensor], name: str, dtype, ref: Tensor) -> None:
+    if t is not None and (_rows(t, name, dtype) != _rows(ref, "x", ref.dtype) or t.device != ref.device):
+        raise ValueError(f"{name} must have the shape, row stride and device of the values")
+
+
+def _groups(group: Optional[Tensor], n_groups: Optional[int], n_rows: int, ref: Tensor) -> int:
+    if group is None:
+        if n_groups not in (None, n_rows):
+            raise ValueError(f"without group every row is a group: n_groups must be {n_rows}")
+        return n_rows
+    if group.dtype != torch.int32 or group.dim() != 1 or group.numel() != n_rows or not group.is_contiguous() \
+            or group.device != ref.device:
+        raise ValueError(f"group must be a contiguous int32 vector of {n_rows} entries on {ref.device}")
+    if n_groups is None or not 1 <= n_groups <= n_rows:
+        raise ValueError(f"with group, n_groups must be given in [1, {n_rows}]")
+    return int(n_groups)
+
+
+def _out(t: Optional[Tensor], name: str, dtype, numel: int, ref: Tensor) -> None:
+    if t is not None and (t.dtype != dtype or t.numel() != numel or not t.is_contiguous() or t.device != ref.device):
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of {numel} entries on {ref.device}")
+
+
+def select_workspace_bytes(n_groups: int, n_ranks: int) -> int:
+    """sr_select_workspace (0 for counts outside the ranges)."""
+    return int(_lib.load().sr_select_workspace(int(n_groups), int(n_ranks)))
+
+
+def select_ranks(x: Tensor, ranks, value: Tensor, *, mask: Optional[Tensor] = None, group: Optional[Tensor] = None,
+                 n_groups: Optional[int] = None, count: Optional[Tensor] = None, blocks_per_row: int = 0) -> None:
+    """sr_select_ranks: for every group of rows of ``x`` [rows, length] fp32 (row r is group ``group[r]``,
+    or group r) the exact order statistics ``ranks`` = ((num, den), ...) of its finite elements whose
+    ``mask`` byte (uint8, same shape and row stride) is non-zero, into ``value`` [n_groups, n_ranks] fp32
+    and, if given, ``count`` [n_groups, 2] int32 (considered, skipped)."""
+    d = _lib.SelectDesc()
+    n_rows, row_len, stride = _rows(x, "x", torch.float32)
+    _like_rows(mask, "mask", torch.uint8, x)
+    ng = _groups(group, n_groups, n_rows, x)
+    ranks = [(int(n), int(m)) for n, m in ranks]
+    if not 1 <= len(ranks) <= 4:
+        raise ValueError(f"1 to 4 ranks are selected at once, got {len(ranks)}")
+    _out(value, "value", torch.float32, ng * len(ranks), x)
+    _out(count, "count", torch.int32, ng * 2, x)
+    need = select_workspace_bytes(ng, len(ranks))
+    ws = torch.empty(need, device=x.device, dtype=torch.uint8)  # stream-ordered: the caching allocator's rule
+    d.x, d.mask, d.group = _p(x), _p(mask), _p(group)
+    d.n_rows, d.row_len, d.row_stride, d.n_groups, d.n_ranks = n_rows, row_len, stride, ng, len(ranks)
+    for k, (n, m) in enumerate(ranks):
+        d.rank_num[k], d.rank_den[k] = n, m
+    d.blocks_per_row, d.value, d.count = int(blocks_per_row), _p(value), _p(count)
+    d.workspace, d.workspace_bytes = _p(ws), need
+    check(_lib.load().sr_select_ranks(_stream(x), ctypes.byref(d)), "sr_select_ranks")
+
+
+def depth_eval_workspace_bytes(n_views: int, n_pix: int, stride: int, n_groups: int, rel_q_scratch: bool = False) -> int:
+    """sr_depth_eval_workspace (0 for arguments sr_depth_eval rejects)."""
+    return int(_lib.load().sr_depth_eval_workspace(int(n_views), int(n_pix), int(stride), int(n_groups),
+                                                   int(bool(rel_q_scratch))))
+
+
+def depth_eval(pred: Tensor, gt: Tensor, *, align: str, xform: Tensor, status: Tensor, stats: Tensor, hist: Tensor,
+               bin_len: float, mask: Optional[Tensor] = None, conf: Optional[Tensor] = None,
+               conf_min: Optional[Tensor] = None, group: Optional[Tensor] = None, n_groups: Optional[int] = None,
+               gt_min: float = 0.0, gt_max: float = float("inf"), aligned: Optional[Tensor] = None,
+               rel_err: Optional[Tensor] = None, rel_q: Optional[Tensor] = None) -> None:
+    """sr_depth_eval: ``pred`` / ``gt`` [views, pixels] fp32 (contiguous rows, one row stride) scored per
+    group of views under ``align`` (a key of DEPTH_ALIGN).  ``xform`` [n_groups, 2] fp64 (s, t; read under
+    "given"), ``status`` [n_groups] int32, ``stats`` [n_groups + 1, 16] fp64, ``hist`` [n_groups + 1,
+    n_bins + 2] (int32 storage of the uint32 counts, zeroed by the call); optional ``aligned`` / ``rel_err``
+    [views, pixels] fp32 and ``rel_q`` [n_groups + 1, 2] fp32.  The last row of stats, hist and rel_q
+    pools the groups."""
+    if align not in DEPTH_ALIGN:
+        raise ValueError(f"align must be one of {sorted(DEPTH_ALIGN)}, got {align!r}")
+    d = _lib.DepthEvalDesc()
+    nv, n_pix, stride = _rows(pred, "pred", torch.float32)
+    _like_rows(gt, "gt", torch.float32, pred)
+    _like_rows(mask, "mask", torch.uint8, pred)
+    _like_rows(conf, "conf", torch.float32, pred)
+    if (conf is None) != (conf_min is None):
+        raise ValueError("conf and conf_min go together")
+    _out(conf_min, "conf_min", torch.float32, nv, pred)
+    ng = _groups(group, n_groups, nv, pred)
+    if hist.dim() != 2 or hist.shape[0] != ng + 1 or hist.shape[1] < 3:
+        raise ValueError(f"hist must be [{ng + 1}, n_bins + 2], got {tuple(hist.shape)}")
+    _out(hist, "hist", torch.int32, hist.numel(), pred)
+    _out(xform, "xform", torch.float64, 2 * ng, pred)
+    _out(status, "status", torch.int32, ng, pred)
+    _out(stats, "stats", torch.float64, 16 * (ng + 1), pred)
+    _out(aligned, "aligned", torch.float32, nv * n_pix, pred)
+    _out(rel_err, "rel_err", torch.float32, nv * n_pix, pred)
+    _out(rel_q, "rel_q", torch.float32, 2 * (ng + 1), pred)
+    need = depth_eval_workspace_bytes(nv, n_pix, stride, ng, rel_q is not None and rel_err is None)
+    if need <= 0:
+        raise ValueError(f"{nv} views of {n_pix} pixels (stride {stride}) in {ng} groups are outside the scorer's ranges")
+    ws = torch.empty(need, device=pred.device, dtype=torch.uint8)  # stream-ordered: the caching allocator's rule
+    d.pred, d.gt, d.mask, d.conf, d.conf_min, d.group = _p(pred), _p(gt), _p(mask), _p(conf), _p(conf_min), _p(group)
+    d.n_pix, d.stride, d.n_views, d.n_groups = n_pix, stride, nv, ng
+    d.gt_min, d.gt_max, d.align = float(gt_min), float(gt_max), DEPTH_ALIGN[align]
+    d.n_bins, d.bin_len = hist.shape[1] - 2, float(bin_len)
+    d.xform, d.status, d.stats, d.hist = _p(xform), _p(status), _p(stats), _p(hist)
+    d.aligned, d.rel_err, d.rel_q = _p(aligned), _p(rel_err), _p(rel_q)
+    d.workspace, d.workspace_bytes = _p(ws), need
+    check(_lib.load().sr_depth_eval(_stream(pred), ctypes.byref(d)), "sr_depth_eval")
+
+
 # ---------------------------------------------------------------- training step (SURVEY §8(f) rank 4)
 _TRAIN_WS = {}  # ((device, stream), name) -> fp32 workspace
 

@@ -6,6 +6,7 @@ What the reference hands to its ``eval`` package after ``save_pointcloud_with_pl
 reconstruction papers report after a similarity alignment.
 
     nn_distances             distance of every query point to its nearest target (and its index)
+    distance_quantiles       exact order statistics (median, p90, ...) of those distances, on the device
     scores_from_hists        accuracy / completeness / Chamfer / precision / recall / F-score, derived on
                              the host from the two device histograms and moment vectors alone
     cloud_accuracy           both directions of one (pred, gt) and the scores, one D2H copy
@@ -98,6 +99,17 @@ def nn_distances(query, target, *, query_xform=None, target_xform=None, return_i
     ops.cloud_nn(q, t, query_xform=_as_xform(query_xform, dev, "query_xform"),
                  target_xform=_as_xform(target_xform, dev, "target_xform"), dist=dist, index=index)
     return (dist, index) if return_index else dist
+
+
+def distance_quantiles(dist, fractions: Sequence = (0.5, 0.9)) -> Tensor:
+    """[len(fractions)] fp32 on the device: the exact order statistics of the finite entries of
+    ``nn_distances``' output (sr_select_ranks: the ascending element max(ceil(q n) - 1, 0), so 0.5 is the
+    lower median), which the histogram only brackets to a bin.  NaN if no distance is finite."""
+    from .depth_eval import select_quantiles
+    d = torch.as_tensor(dist)
+    if d.dim() != 1 or d.numel() == 0:
+        raise ValueError(f"dist must be a non-empty vector, got {tuple(d.shape)}")
+    return select_quantiles(d[None], fractions)[0]
 
 
 def _side(hist, stats, name: str):

@@ -974,6 +974,84 @@ def cloud(runs=3):
           f"{float((baseline(q, t).double() - ref).abs().max()):.3e}", flush=True)
 
 
+def depth(runs=3):
+    """Depth-map scoring (sr_depth_eval: MEDIAN alignment, a group per view, a validity mask) against the
+    torch statement (masked ``torch.median`` per view, the metrics in fp32, one ``.item()`` per metric),
+    in alternation in one process, ``runs`` timed runs each after one warm-up, HIP events.  Two pairs:
+    every output (aligned, rel_err and the exact median / p90 of rel) against the statement with
+    ``median`` / ``kthvalue`` of rel, and the sums, counts and histogram alone against the statement
+    without them.  Shapes: 64 x 518 x 518 and 5 x 518 x 518.  Effective GB/s = the bytes read once (pred,
+    gt, mask: 9 per pixel) over the time, beside the 6.3 TB/s a streaming kernel reaches on this part
+    (MI355X_MICROARCH "HBM").  Then sr_select_ranks alone (median and p90 of one [64, 518 x 518] fp32
+    tensor, 4 bytes per element read once) for the automatic and explicit workgroups per row."""
+    g = torch.Generator(device=DEV).manual_seed(0)
+    ln10 = 2.302585092994046
+
+    def kernel(p, gt, m, full):
+        nv, n = p.shape
+        xf = torch.empty(nv, 2, device=DEV, dtype=torch.float64)
+        status = torch.empty(nv, device=DEV, dtype=torch.int32)
+        stats = torch.empty(nv + 1, 16, device=DEV, dtype=torch.float64)
+        hist = torch.empty(nv + 1, 1026, device=DEV, dtype=torch.int32)
+        extra = {}
+        if full:
+            extra = dict(aligned=torch.empty(nv, n, device=DEV), rel_err=torch.empty(nv, n, device=DEV),
+                         rel_q=torch.empty(nv + 1, 2, device=DEV))
+        ops.depth_eval(p, gt, align="median", xform=xf, status=status, stats=stats, hist=hist, bin_len=0.005, mask=m, **extra)
+        return torch.cat([stats.reshape(-1), xf.reshape(-1)]).cpu()  # the one D2H copy
+
+    def statement(p, gt, m, full):
+        out = []
+        for v in range(p.shape[0]):
+            ok = m[v].bool() & torch.isfinite(gt[v]) & (gt[v] > 0) & torch.isfinite(p[v])
+            pv, gv = p[v][ok], gt[v][ok]
+            a = pv * (gv.median() / pv.median())
+            e = a - gv
+            rel, d, r = e.abs() / gv, a.log() - gv.log(), torch.maximum(a / gv, gv / a)
+            vals = [rel.mean(), (e * e / gv).mean(), (e * e).mean().sqrt(), (d * d).mean().sqrt(),
+                    100 * d.var(unbiased=False).sqrt(), d.abs().mean() / ln10, (r < 1.25).float().mean(),
+                    (r < 1.5625).float().mean(), (r < 1.953125).float().mean()]
+            if full:
+                vals += [rel.median(), rel.kthvalue((9 * rel.numel() + 9) // 10).values]
+            out.append([x.item() for x in vals])
+        return out
+
+    for nv in (64, 5):
+        n = 518 * 518
+        gt = torch.rand(nv, n, device=DEV, generator=g) * 5 + 1
+        p = (gt * (1 + 0.05 * torch.randn(nv, n, device=DEV, generator=g)) - 0.05) / 1.1
+        gt[:, ::17] = 0
+        m = (torch.rand(nv, n, device=DEV, generator=g) > 0.03).to(torch.uint8)
+        fns = {"sr_depth_eval, every output": lambda: kernel(p, gt, m, True),
+               "torch statement with rel quantiles": lambda: statement(p, gt, m, True),
+               "sr_depth_eval, sums and histogram": lambda: kernel(p, gt, m, False),
+               "torch statement": lambda: statement(p, gt, m, False)}
+        times = {k: [] for k in fns}
+        for fn in fns.values():
+            fn()
+        torch.cuda.synchronize()
+        for _ in range(runs):
+            for name, fn in fns.items():
+                times[name].append(timeit(fn, reps=1, warm=0))
+        for name, ms in times.items():
+            print(f"depth {nv} x 518 x 518 {name:35s}: " + " ".join(f"{t:8.3f}" for t in ms) + f" ms  best {min(ms):8.3f} ms  "
+                  f"{9 * nv * n / (min(ms) * 1e-3) / 1e9:8.1f} GB/s effective (HBM streaming: 6300)", flush=True)
+        k, s = kernel(p, gt, m, True), statement(p, gt, m, True)
+        abs_rel = (k[:nv * 16].reshape(nv, 16)[:, 3] / k[:nv * 16].reshape(nv, 16)[:, 0]).numpy()
+        print(f"depth {nv} x 518 x 518: every output {min(times['torch statement with rel quantiles']) / min(times['sr_depth_eval, every output']):.1f} x, "
+              f"sums and histogram {min(times['torch statement']) / min(times['sr_depth_eval, sums and histogram']):.1f} x the "
+              f"statement's speed; largest abs_rel difference {max(abs(abs_rel[v] - s[v][0]) for v in range(nv)):.2e}  "
+              f"[{ops.last_kernel()}]", flush=True)
+        if nv == 64:
+            value = torch.empty(nv, 2, device=DEV)
+            for bpr in (0, 1, 4, 16, 66, 262):
+                ms = [timeit(lambda: ops.select_ranks(p, [(1, 2), (9, 10)], value, blocks_per_row=bpr), reps=1, warm=0)
+                      for _ in range(runs + 1)][1:]
+                print(f"select 64 x 518 x 518, 2 ranks, blocks_per_row {bpr:3d}: " + " ".join(f"{t:7.3f}" for t in ms) +
+                      f" ms  best {min(ms):7.3f} ms  {4 * nv * n / (min(ms) * 1e-3) / 1e9:8.1f} GB/s effective, 4 passes", flush=True)
+        del gt, p, m
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["attn", "gemm", "ln"]
     for w in which:
