@@ -1198,6 +1198,105 @@ int64_t sr_depth_eval_workspace(int n_views, int64_t n_pix, int64_t stride, int 
  * that is not 8-byte aligned. */
 int sr_depth_eval(sr_stream_t stream, const sr_depth_eval_desc* desc);
 
+/* ------------------------------------------------------------------------------------------
+ * Stable device-wide sort of (key, value) pairs (ABI 1.13): a least-significant-digit radix sort on
+ * 64-bit unsigned keys.  Definitions: DESIGN.md "Downsampling point clouds", csrc/sr_sort.hip.
+ *   order       that of key & (2^key_bits - 1), unsigned, ascending; equal masked keys keep ascending
+ *               input position: vals_out is np.argsort(keys & mask, kind="stable") when vals_in is NULL,
+ *               and vals_in gathered by that permutation otherwise
+ *   keys_out    the whole keys in that order: bits above key_bits ride along and never decide it
+ *   passes      ceil(key_bits / 8), 8 bits each, three launches per pass: the digit histogram of every
+ *               tile of 2048 elements, an exclusive scan of the digit-major [256][tiles] table (one
+ *               workgroup per digit), and the scatter.  An element's rank among its tile's equal digits
+ *               comes from wave ballots and per-wave counters combined in wave order; integer atomics
+ *               only add the 256 digit totals, whose sum does not depend on their order.  No kernel
+ *               waits on another workgroup.  Every scattered store is guarded by position < n.  Any two
+ *               runs give the same bits.
+ *   Inputs are not written; the passes ping-pong through the workspace.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct sr_sort_desc {
+  const uint64_t* keys_in;    /* [n] */
+  const uint32_t* vals_in;    /* [n], or NULL: element i carries i (the result is the sorting permutation) */
+  uint64_t* keys_out;         /* [n] whole keys in sorted order, or NULL */
+  uint32_t* vals_out;         /* [n] */
+  int64_t n;                  /* 1 .. 2^31 - 1 */
+  int key_bits;               /* 1 .. 64: the order is that of key & (2^key_bits - 1), unsigned */
+  void* workspace;            /* >= sr_sort_workspace(n) bytes, 16-byte aligned, stream-ordered reuse */
+  int64_t workspace_bytes;
+} sr_sort_desc;
+
+/* Bytes of workspace: two key and two value buffers of n elements, the [256][tiles] table and the digit
+ * totals of the eight passes.  Never shrinks when n grows; 0 for n outside [1, 2^31 - 1]. */
+int64_t sr_sort_workspace(int64_t n);
+/* One clearing node and three launches per pass, asynchronous and allocation-free.  SR_EINVAL for a null
+ * desc, keys_in, vals_out or workspace; n outside [1, 2^31 - 1]; key_bits outside [1, 64]; an output
+ * pointer equal to an input pointer (keys_out == keys_in, vals_out == vals_in); a key pointer that is not
+ * 8-byte or a value pointer that is not 4-byte aligned; a workspace that is too small or not 16-byte
+ * aligned. */
+int sr_sort_pairs(sr_stream_t stream, const sr_sort_desc* desc);
+
+/* ------------------------------------------------------------------------------------------
+ * Downsampling a point cloud to a voxel grid (ABI 1.13): points in, one point per occupied voxel out,
+ * in a fixed order.  Definitions: DESIGN.md "Downsampling point clouds", csrc/sr_cloud_voxel.hip.
+ *   skipped     the mask byte is 0; a coordinate is non-finite (a test on the bits); under BEST, the weight
+ *               is a NaN; the transformed point is non-finite
+ *   transform   q = p without xform, else fl32(s (R p) + t) by sr_cloud_nn's rule: fp64, left to right,
+ *               nothing contracted, rounded once
+ *   cell        per axis f = floor(((double)q - origin) / voxel) in IEEE fp64, a true division
+ *   considered  -2^(b-1) <= f < 2^(b-1) on all three axes, b = axis_bits, compared in fp64 before any
+ *               conversion to an integer.  Every other point that is not skipped is outside.
+ *   key         (u_z << 2b) | (u_y << b) | u_x, u = f + 2^(b-1).  Output rows are in ascending key order
+ *               (z-major, then y, then x); the members of a voxel are in ascending input index.
+ *   MEAN        per coordinate and attribute column: the fp64 sum of the members' fp32 values, left to
+ *               right in ascending index, divided by (double)count, rounded to fp32 once; out_index is the
+ *               lowest member index
+ *   BEST        the member with the largest weight; equal weights (-0 = +0) and a NULL weight: the lowest
+ *               index.  Its q and attributes are copied bit for bit; out_index is its index.
+ *   Attributes are specified for finite values.
+ *   Rows at or beyond capacity are never written; counts[0] and voxel_of still report the true numbers.
+ *   Kernels: keys (sentinel 2^(3b) for what is not considered), sr_sort_pairs' passes on 3b + 1 bits,
+ *   head flags as per-tile counts, a one-workgroup scan of the counts and a local scan, then one lane
+ *   per voxel walking its members.  Integer atomics only (the three counts), no waiting on another
+ *   workgroup: any two runs give the same bits.
+ * ------------------------------------------------------------------------------------------ */
+enum sr_voxel_mode { SR_VOXEL_MEAN = 0, SR_VOXEL_BEST = 1 };
+#define SR_VOXEL_MAX_ATTR 8
+typedef struct sr_cloud_voxel_desc {
+  const float* points;        /* [n][ldp] fp32 */
+  const float* attr;          /* [n][lda] fp32, or NULL (n_attr == 0) */
+  const uint8_t* mask;        /* [n] bytes, 0 = skip, or NULL */
+  const float* weight;        /* [n] fp32, SR_VOXEL_BEST only, or NULL */
+  const double* xform;        /* device [13]: scale, R row-major, t -- sr_pose_align's out[0..12] -- or NULL */
+  int64_t n;                  /* 1 .. 2^31 - 1 */
+  int64_t ldp;                /* floats between points, >= 3 */
+  int64_t lda;                /* floats between attribute rows, >= n_attr */
+  int n_attr;                 /* 0 .. SR_VOXEL_MAX_ATTR columns used */
+  int axis_bits;              /* b: 1 .. 21 */
+  int mode;                   /* sr_voxel_mode */
+  double origin[3];           /* finite */
+  double voxel;               /* finite, > 0 */
+  int64_t capacity;           /* rows of the outputs, 1 .. n */
+  float* out_points;          /* [capacity][3] */
+  float* out_attr;            /* [capacity][n_attr], or NULL */
+  uint32_t* out_count;        /* [capacity] members, or NULL */
+  uint32_t* out_index;        /* [capacity], or NULL */
+  uint64_t* out_key;          /* [capacity], or NULL */
+  int32_t* voxel_of;          /* [n] the element's output row, -1 if it is not considered; or NULL */
+  uint32_t* counts;           /* [4] voxels, considered, skipped, outside; or NULL */
+  void* workspace;            /* >= sr_cloud_voxel_workspace(n) bytes, 16-byte aligned, stream-ordered reuse */
+  int64_t workspace_bytes;
+} sr_cloud_voxel_desc;
+
+/* Bytes of workspace: keys, sorted keys, the permutation, the voxel starts, the per-tile head counts, the
+ * four counts and sr_sort_workspace(n).  Never shrinks when n grows; 0 for n outside [1, 2^31 - 1]. */
+int64_t sr_cloud_voxel_workspace(int64_t n);
+/* Asynchronous and allocation-free.  SR_EINVAL for a null desc, points, out_points or workspace; n outside
+ * [1, 2^31 - 1]; ldp < 3; n_attr outside [0, 8]; n_attr > 0 with a NULL attr or lda < n_attr; a weight
+ * under SR_VOXEL_MEAN; a mode outside sr_voxel_mode; axis_bits outside [1, 21]; an origin or voxel that is
+ * not finite, or voxel <= 0; capacity outside [1, n]; a workspace that is too small or not 16-byte
+ * aligned; an fp64 or 64-bit pointer (xform, out_key) that is not 8-byte aligned. */
+int sr_cloud_voxel(sr_stream_t stream, const sr_cloud_voxel_desc* desc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@
 //   abi_host_check layout imc_stats   the same for sr_imc_stats_desc (ABI 1.10)
 //   abi_host_check layout cloud_eval   the same for sr_cloud_nn_desc (ABI 1.11)
 //   abi_host_check layout depth_eval   the same for sr_select_desc and sr_depth_eval_desc (ABI 1.12)
+//   abi_host_check layout cloud_voxel   the same for sr_sort_desc and sr_cloud_voxel_desc (ABI 1.13)
 //   abi_host_check check    the validation sweep; exit 0 iff every call returned what it should
 #include <cstddef>
 #include <cstdio>
@@ -187,6 +188,25 @@ void layout_depth_eval() {
           FIELD(sr_depth_eval_desc, xform), FIELD(sr_depth_eval_desc, status), FIELD(sr_depth_eval_desc, stats),
           FIELD(sr_depth_eval_desc, hist), FIELD(sr_depth_eval_desc, aligned), FIELD(sr_depth_eval_desc, rel_err),
           FIELD(sr_depth_eval_desc, rel_q), FIELD(sr_depth_eval_desc, workspace), FIELD(sr_depth_eval_desc, workspace_bytes)));
+  std::printf("}\n");
+}
+
+void layout_cloud_voxel() {
+  const char* sep = "";
+  std::printf("{");
+  STRUCT(sr_sort_desc,
+         (FIELD(sr_sort_desc, keys_in), FIELD(sr_sort_desc, vals_in), FIELD(sr_sort_desc, keys_out),
+          FIELD(sr_sort_desc, vals_out), FIELD(sr_sort_desc, n), FIELD(sr_sort_desc, key_bits),
+          FIELD(sr_sort_desc, workspace), FIELD(sr_sort_desc, workspace_bytes)));
+  STRUCT(sr_cloud_voxel_desc,
+         (FIELD(sr_cloud_voxel_desc, points), FIELD(sr_cloud_voxel_desc, attr), FIELD(sr_cloud_voxel_desc, mask),
+          FIELD(sr_cloud_voxel_desc, weight), FIELD(sr_cloud_voxel_desc, xform), FIELD(sr_cloud_voxel_desc, n),
+          FIELD(sr_cloud_voxel_desc, ldp), FIELD(sr_cloud_voxel_desc, lda), FIELD(sr_cloud_voxel_desc, n_attr),
+          FIELD(sr_cloud_voxel_desc, axis_bits), FIELD(sr_cloud_voxel_desc, mode), FIELD(sr_cloud_voxel_desc, origin),
+          FIELD(sr_cloud_voxel_desc, voxel), FIELD(sr_cloud_voxel_desc, capacity), FIELD(sr_cloud_voxel_desc, out_points),
+          FIELD(sr_cloud_voxel_desc, out_attr), FIELD(sr_cloud_voxel_desc, out_count), FIELD(sr_cloud_voxel_desc, out_index),
+          FIELD(sr_cloud_voxel_desc, out_key), FIELD(sr_cloud_voxel_desc, voxel_of), FIELD(sr_cloud_voxel_desc, counts),
+          FIELD(sr_cloud_voxel_desc, workspace), FIELD(sr_cloud_voxel_desc, workspace_bytes)));
   std::printf("}\n");
 }
 
@@ -889,6 +909,147 @@ void check() {
     c = dd, c.stats = (double*)((char*)fake(8) + 4);
     expect("sr_depth_eval stats % 8", sr_depth_eval(nullptr, &c), false);
   }
+  {
+    // ---- sr_sort_pairs / sr_cloud_voxel (ABI 1.13)
+    const int64_t big = 32LL * 518 * 518, most = 2147483647LL;
+    {  // never shrinks when n grows; 0 outside the range
+      const int64_t ns[] = {1, 2, 63, 64, 65, 2047, 2048, 2049, 4097, 70001, 5LL * 518 * 518, big, 1LL << 30, most};
+      int64_t ps = 0, pv = 0;
+      for (int64_t n : ns) {
+        const int64_t s = sr_sort_workspace(n), v = sr_cloud_voxel_workspace(n);
+        if (s <= 0 || s % 16 || s < ps || s < 24 * n || v < s + 24 * n || v % 16 || v < pv) ++g_fail;
+        ps = s, pv = v;
+      }
+      for (int64_t n : {int64_t(0), int64_t(-1), most + 1, int64_t(1) << 40})
+        if (sr_sort_workspace(n) != 0 || sr_cloud_voxel_workspace(n) != 0) ++g_fail;
+      std::printf("sort / voxel workspace bytes at 32 x 518 x 518: %lld / %lld\n", (long long)sr_sort_workspace(big),
+                  (long long)sr_cloud_voxel_workspace(big));
+    }
+    sr_sort_desc so{};
+    so.keys_in = fake<uint64_t>(0), so.vals_in = fake<uint32_t>(1), so.keys_out = fake<uint64_t>(2);
+    so.vals_out = fake<uint32_t>(3), so.n = big, so.key_bits = 64, so.workspace = fake(4);
+    so.workspace_bytes = sr_sort_workspace(big);
+    expect("sr_sort_pairs 32 x 518 x 518, 64 bits", sr_sort_pairs(nullptr, &so), true);
+    sr_sort_desc t = so;
+    for (int bits : {1, 7, 8, 9, 16, 31, 33, 63}) {
+      t = so, t.key_bits = bits;
+      expect("sr_sort_pairs key_bits sweep", sr_sort_pairs(nullptr, &t), true);
+    }
+    for (int64_t n : {int64_t(1), int64_t(2), int64_t(2048), int64_t(2049), int64_t(70001)}) {
+      t = so, t.n = n;
+      expect("sr_sort_pairs n sweep", sr_sort_pairs(nullptr, &t), true);
+    }
+    t = so, t.vals_in = nullptr, t.keys_out = nullptr;
+    expect("sr_sort_pairs permutation only", sr_sort_pairs(nullptr, &t), true);
+    t = so, t.n = most, t.workspace_bytes = sr_sort_workspace(most);
+    expect("sr_sort_pairs 2^31 - 1", sr_sort_pairs(nullptr, &t), true);
+    expect("sr_sort_pairs null desc", sr_sort_pairs(nullptr, nullptr), false);
+    t = so, t.keys_in = nullptr;
+    expect("sr_sort_pairs null keys_in", sr_sort_pairs(nullptr, &t), false);
+    t = so, t.vals_out = nullptr;
+    expect("sr_sort_pairs null vals_out", sr_sort_pairs(nullptr, &t), false);
+    t = so, t.workspace = nullptr;
+    expect("sr_sort_pairs null workspace", sr_sort_pairs(nullptr, &t), false);
+    t = so, t.n = 0;
+    expect("sr_sort_pairs n 0", sr_sort_pairs(nullptr, &t), false);
+    t = so, t.n = most + 1, t.workspace_bytes = int64_t(1) << 50;
+    expect("sr_sort_pairs n 2^31", sr_sort_pairs(nullptr, &t), false);
+    t = so, t.key_bits = 0;
+    expect("sr_sort_pairs key_bits 0", sr_sort_pairs(nullptr, &t), false);
+    t = so, t.key_bits = 65;
+    expect("sr_sort_pairs key_bits 65", sr_sort_pairs(nullptr, &t), false);
+    t = so, t.keys_out = fake<uint64_t>(0);
+    expect("sr_sort_pairs keys_out == keys_in", sr_sort_pairs(nullptr, &t), false);
+    t = so, t.vals_out = fake<uint32_t>(1);
+    expect("sr_sort_pairs vals_out == vals_in", sr_sort_pairs(nullptr, &t), false);
+    t = so, t.keys_in = (const uint64_t*)((const char*)fake(0) + 4);
+    expect("sr_sort_pairs keys_in % 8", sr_sort_pairs(nullptr, &t), false);
+    t = so, t.vals_out = (uint32_t*)((char*)fake(3) + 2);
+    expect("sr_sort_pairs vals_out % 4", sr_sort_pairs(nullptr, &t), false);
+    t = so, t.workspace_bytes -= 1;
+    expect("sr_sort_pairs workspace one byte short", sr_sort_pairs(nullptr, &t), false);
+    t = so, t.workspace = (char*)fake(4) + 8;
+    expect("sr_sort_pairs workspace % 16", sr_sort_pairs(nullptr, &t), false);
+
+    sr_cloud_voxel_desc vd{};
+    vd.points = fake<float>(0), vd.attr = fake<float>(1), vd.mask = fake<uint8_t>(2), vd.weight = fake<float>(3);
+    vd.xform = fake<double>(4), vd.n = big, vd.ldp = 3, vd.lda = 4, vd.n_attr = 4, vd.axis_bits = 21;
+    vd.mode = SR_VOXEL_BEST, vd.origin[0] = 0.1, vd.origin[1] = -0.2, vd.origin[2] = 0.3, vd.voxel = 0.01;
+    vd.capacity = big, vd.out_points = fake<float>(5), vd.out_attr = fake<float>(6), vd.out_count = fake<uint32_t>(7);
+    vd.out_index = fake<uint32_t>(8), vd.out_key = fake<uint64_t>(9), vd.voxel_of = fake<int32_t>(10);
+    vd.counts = fake<uint32_t>(11), vd.workspace = fake(12), vd.workspace_bytes = sr_cloud_voxel_workspace(big);
+    expect("sr_cloud_voxel 32 x 518 x 518 BEST, every output", sr_cloud_voxel(nullptr, &vd), true);
+    sr_cloud_voxel_desc u = vd;
+    u = vd, u.mode = SR_VOXEL_MEAN, u.weight = nullptr;
+    expect("sr_cloud_voxel MEAN", sr_cloud_voxel(nullptr, &u), true);
+    u = vd, u.attr = nullptr, u.n_attr = 0, u.mask = nullptr, u.weight = nullptr, u.xform = nullptr, u.out_attr = nullptr;
+    u.out_count = nullptr, u.out_index = nullptr, u.out_key = nullptr, u.voxel_of = nullptr, u.counts = nullptr;
+    expect("sr_cloud_voxel bare", sr_cloud_voxel(nullptr, &u), true);
+    for (int b : {1, 4, 20}) {
+      u = vd, u.axis_bits = b, u.ldp = 4, u.lda = 9, u.n_attr = 8, u.capacity = 1;
+      expect("sr_cloud_voxel axis_bits sweep, padded rows, capacity 1", sr_cloud_voxel(nullptr, &u), true);
+    }
+    u = vd, u.n = 1, u.capacity = 1;
+    expect("sr_cloud_voxel one point", sr_cloud_voxel(nullptr, &u), true);
+    u = vd, u.n = most, u.capacity = 5, u.workspace_bytes = sr_cloud_voxel_workspace(most);
+    expect("sr_cloud_voxel 2^31 - 1 points", sr_cloud_voxel(nullptr, &u), true);
+    expect("sr_cloud_voxel null desc", sr_cloud_voxel(nullptr, nullptr), false);
+    u = vd, u.points = nullptr;
+    expect("sr_cloud_voxel null points", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, u.out_points = nullptr;
+    expect("sr_cloud_voxel null out_points", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, u.workspace = nullptr;
+    expect("sr_cloud_voxel null workspace", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, u.n = 0;
+    expect("sr_cloud_voxel n 0", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, u.n = most + 1, u.workspace_bytes = int64_t(1) << 50;
+    expect("sr_cloud_voxel n 2^31", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, u.ldp = 2;
+    expect("sr_cloud_voxel ldp 2", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, u.n_attr = -1;
+    expect("sr_cloud_voxel n_attr -1", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, u.n_attr = 9, u.lda = 9;
+    expect("sr_cloud_voxel n_attr 9", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, u.attr = nullptr;
+    expect("sr_cloud_voxel n_attr without attr", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, u.lda = 3;
+    expect("sr_cloud_voxel lda < n_attr", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, u.mode = SR_VOXEL_MEAN;
+    expect("sr_cloud_voxel weight under MEAN", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, u.mode = 2;
+    expect("sr_cloud_voxel mode 2", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, u.mode = -1;
+    expect("sr_cloud_voxel mode -1", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, u.axis_bits = 0;
+    expect("sr_cloud_voxel axis_bits 0", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, u.axis_bits = 22;
+    expect("sr_cloud_voxel axis_bits 22", sr_cloud_voxel(nullptr, &u), false);
+    const uint64_t inf64 = 0x7ff0000000000000ull, nan64 = 0x7ff8000000000000ull;
+    u = vd, std::memcpy(&u.origin[1], &nan64, 8);
+    expect("sr_cloud_voxel origin NaN", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, std::memcpy(&u.origin[2], &inf64, 8);
+    expect("sr_cloud_voxel origin Inf", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, u.voxel = 0.0;
+    expect("sr_cloud_voxel voxel 0", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, u.voxel = -1.0;
+    expect("sr_cloud_voxel voxel -1", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, std::memcpy(&u.voxel, &inf64, 8);
+    expect("sr_cloud_voxel voxel Inf", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, std::memcpy(&u.voxel, &nan64, 8);
+    expect("sr_cloud_voxel voxel NaN", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, u.capacity = 0;
+    expect("sr_cloud_voxel capacity 0", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, u.capacity = big + 1;
+    expect("sr_cloud_voxel capacity n + 1", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, u.workspace_bytes -= 1;
+    expect("sr_cloud_voxel workspace one byte short", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, u.workspace = (char*)fake(12) + 8;
+    expect("sr_cloud_voxel workspace % 16", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, u.xform = (const double*)((const char*)fake(4) + 4);
+    expect("sr_cloud_voxel xform % 8", sr_cloud_voxel(nullptr, &u), false);
+    u = vd, u.out_key = (uint64_t*)((char*)fake(9) + 4);
+    expect("sr_cloud_voxel out_key % 8", sr_cloud_voxel(nullptr, &u), false);
+  }
   expect("sr_pose_decode_f32 null", sr_pose_decode_f32(nullptr, nullptr, 9, 0, 518, 518, nullptr, nullptr), false);
   expect("sr_copy_rows_f32 null", sr_copy_rows_f32(nullptr, nullptr, 0, nullptr, 0, nullptr, 0, 0), false);
   expect("sr_conv3x3_f32 null", sr_conv3x3_f32(nullptr, nullptr, 1, 8, 8, 32, 1, 0, nullptr, 32, SR_EPI_BIAS, &ep, nullptr, 32, nullptr), false);
@@ -966,6 +1127,8 @@ int main(int argc, char** argv) {
       layout_cloud_eval();
     else if (argc > 2 && std::string(argv[2]) == "depth_eval")
       layout_depth_eval();
+    else if (argc > 2 && std::string(argv[2]) == "cloud_voxel")
+      layout_cloud_voxel();
     else
       layout();
     return 0;

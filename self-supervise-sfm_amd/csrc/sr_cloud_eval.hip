@@ -56,17 +56,7 @@ constexpr int AUTO_MIN_CHUNK = 2048;  // fewest targets of an automatic slice
 __device__ inline bool bits_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
 __device__ inline float pos_inf() { return __uint_as_float(0x7f800000u); }
 
-// fl32(s (R p) + t): fp64, left to right, no contraction (bit for bit what numpy computes)
-__device__ inline void xform_point(const double* __restrict__ x, float& px, float& py, float& pz) {
-  const double a = (double)px, b = (double)py, c = (double)pz;
-  float o[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    const double rp = __dadd_rn(__dadd_rn(__dmul_rn(x[1 + 3 * r], a), __dmul_rn(x[2 + 3 * r], b)), __dmul_rn(x[3 + 3 * r], c));
-    o[r] = (float)__dadd_rn(__dmul_rn(x[0], rp), x[10 + r]);
-  }
-  px = o[0], py = o[1], pz = o[2];
-}
+using sr::xform_point;  // fl32(s (R p) + t), shared with sr_cloud_voxel (sr_common.h)
 
 // a point of a packed [n][3] array, transformed; true if it is non-finite before or after
 __device__ inline bool load_point(const float* __restrict__ pts, int64_t i, const double* __restrict__ xform, float& x,

@@ -29,6 +29,10 @@ void note_kernel(const char* fmt, ...);
 int tune(int key);
 // compute units of the current device (read once; 256 on MI355X)
 int cu_count();
+// sr_sort_pairs behind its validation (sr_sort.hip), for the entry points that sort inside their own call
+int64_t sort_workspace(int64_t n);
+void sort_launch(hipStream_t s, const uint64_t* keys_in, const uint32_t* vals_in, uint64_t* keys_out, uint32_t* vals_out,
+                 int64_t n, int key_bits, void* workspace);
 
 template <typename T> struct is_bf16 { static constexpr bool value = false; };
 template <> struct is_bf16<bf16> { static constexpr bool value = true; };
@@ -130,6 +134,21 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
+}
+
+// fl32(s (R p) + t) from the fp32 point and the fp64 [13] = scale, R row-major, t: fp64, left to right, rounded
+// to fp32 once.  The one transform of sr_cloud_nn and sr_cloud_voxel.  __dmul_rn / __dadd_rn are plain * and +
+// in the HIP headers, so whether they stay unfused is the including object's -ffp-contract: sr_cloud_voxel.o
+// is built with it off (bit for bit what numpy computes), sr_cloud_eval.o as it always was.
+__device__ inline void xform_point(const double* __restrict__ x, float& px, float& py, float& pz) {
+  const double a = (double)px, b = (double)py, c = (double)pz;
+  float o[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const double rp = __dadd_rn(__dadd_rn(__dmul_rn(x[1 + 3 * r], a), __dmul_rn(x[2 + 3 * r], b)), __dmul_rn(x[3 + 3 * r], c));
+    o[r] = (float)__dadd_rn(__dmul_rn(x[0], rp), x[10 + r]);
+  }
+  px = o[0], py = o[1], pz = o[2];
 }
 
 __device__ __forceinline__ void wait_vmcnt0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }

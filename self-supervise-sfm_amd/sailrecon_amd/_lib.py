@@ -195,6 +195,29 @@ class DepthEvalDesc(ctypes.Structure):
     ]
 
 
+class SortDesc(ctypes.Structure):
+    """sr_sort_desc (include/sfm_amd.h)."""
+    _fields_ = [
+        ("keys_in", _vp), ("vals_in", _vp), ("keys_out", _vp), ("vals_out", _vp), ("n", _i64), ("key_bits", _i32),
+        ("workspace", _vp), ("workspace_bytes", _i64),
+    ]
+
+
+SR_VOXEL_MEAN, SR_VOXEL_BEST = 0, 1
+SR_VOXEL_MAX_ATTR = 8
+
+
+class CloudVoxelDesc(ctypes.Structure):
+    """sr_cloud_voxel_desc (include/sfm_amd.h)."""
+    _fields_ = [
+        ("points", _vp), ("attr", _vp), ("mask", _vp), ("weight", _vp), ("xform", _vp), ("n", _i64), ("ldp", _i64),
+        ("lda", _i64), ("n_attr", _i32), ("axis_bits", _i32), ("mode", _i32), ("origin", ctypes.c_double * 3),
+        ("voxel", ctypes.c_double), ("capacity", _i64), ("out_points", _vp), ("out_attr", _vp), ("out_count", _vp),
+        ("out_index", _vp), ("out_key", _vp), ("voxel_of", _vp), ("counts", _vp), ("workspace", _vp),
+        ("workspace_bytes", _i64),
+    ]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "sr_last_error": (ctypes.c_char_p, []),
@@ -300,6 +323,10 @@ _PROTOS = {
     "sr_select_ranks": (_i32, [_vp, ctypes.POINTER(SelectDesc)]),
     "sr_depth_eval_workspace": (_i64, [_i32, _i64, _i64, _i32, _i32]),
     "sr_depth_eval": (_i32, [_vp, ctypes.POINTER(DepthEvalDesc)]),
+    "sr_sort_workspace": (_i64, [_i64]),
+    "sr_sort_pairs": (_i32, [_vp, ctypes.POINTER(SortDesc)]),
+    "sr_cloud_voxel_workspace": (_i64, [_i64]),
+    "sr_cloud_voxel": (_i32, [_vp, ctypes.POINTER(CloudVoxelDesc)]),
 }
 EXPORTED = tuple(_PROTOS)
 

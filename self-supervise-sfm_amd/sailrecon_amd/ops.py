@@ -1575,6 +1575,107 @@ def depth_eval(pred: Tensor, gt: Tensor, *, align: str, xform: Tensor, status: T
     check(_lib.load().sr_depth_eval(_stream(pred), ctypes.byref(d)), "sr_depth_eval")
 
 
+# ---------------------------------------------------------------- sorting, voxel downsampling (utils/cloud_export.py)
+VOXEL_MODE = {"mean": _lib.SR_VOXEL_MEAN, "best": _lib.SR_VOXEL_BEST}
+_KEY_DTYPES = (torch.int64,) + ((torch.uint64,) if hasattr(torch, "uint64") else ())
+
+
+def sort_workspace_bytes(n: int) -> int:
+    """sr_sort_workspace (0 for n outside [1, 2^31 - 1])."""
+    return int(_lib.load().sr_sort_workspace(int(n)))
+
+
+def sort_pairs(keys: Tensor, values: Optional[Tensor] = None, key_bits: int = 64, *, want_keys: bool = True,
+               out_keys: Optional[Tensor] = None, out_values: Optional[Tensor] = None):
+    """sr_sort_pairs: the stable ascending order of ``keys`` [n] (int64 storage of the unsigned 64-bit keys, or
+    uint64) under ``key & (2^key_bits - 1)``.  Returns ``(sorted_keys, sorted_values)``: the whole keys in that
+    order (None with ``want_keys=False``) and ``values`` [n] int32 carried along, or, without ``values``, the
+    sorting permutation ``argsort(keys & mask, stable)`` as int32.  ``out_keys`` / ``out_values`` receive the
+    results in place of fresh tensors."""
+    if not isinstance(keys, Tensor) or not keys.is_cuda or keys.dtype not in _KEY_DTYPES or keys.dim() != 1 \
+            or not keys.is_contiguous() or keys.numel() == 0:
+        raise ValueError("keys must be a non-empty contiguous 1-D int64 (or uint64) device tensor")
+    n = keys.numel()
+    _out(values, "values", torch.int32, n, keys)
+    _out(out_values, "out_values", torch.int32, n, keys)
+    if out_keys is not None and (out_keys.dtype != keys.dtype or out_keys.numel() != n or not out_keys.is_contiguous()
+                                 or out_keys.device != keys.device):
+        raise ValueError(f"out_keys must be a contiguous {keys.dtype} tensor of {n} entries on {keys.device}")
+    if out_keys is None and want_keys:
+        out_keys = torch.empty_like(keys)
+    if out_values is None:
+        out_values = torch.empty(n, device=keys.device, dtype=torch.int32)
+    need = sort_workspace_bytes(n)
+    ws = torch.empty(max(need, 16), device=keys.device, dtype=torch.uint8)  # stream-ordered: the caching allocator's rule
+    d = _lib.SortDesc()
+    d.keys_in, d.vals_in, d.keys_out, d.vals_out = _p(keys), _p(values), _p(out_keys), _p(out_values)
+    d.n, d.key_bits, d.workspace, d.workspace_bytes = n, int(key_bits), _p(ws), need
+    check(_lib.load().sr_sort_pairs(_stream(keys), ctypes.byref(d)), "sr_sort_pairs")
+    return out_keys, out_values
+
+
+def cloud_voxel_workspace_bytes(n: int) -> int:
+    """sr_cloud_voxel_workspace (0 for n outside [1, 2^31 - 1])."""
+    return int(_lib.load().sr_cloud_voxel_workspace(int(n)))
+
+
+def cloud_voxel(points: Tensor, voxel: float, out_points: Tensor, *, attr: Optional[Tensor] = None,
+                n_attr: Optional[int] = None, mask: Optional[Tensor] = None, weight: Optional[Tensor] = None,
+                xform: Optional[Tensor] = None, origin=(0.0, 0.0, 0.0), axis_bits: int = 21, mode: str = "mean",
+                capacity: Optional[int] = None, out_attr: Optional[Tensor] = None, out_count: Optional[Tensor] = None,
+                out_index: Optional[Tensor] = None, out_key: Optional[Tensor] = None, voxel_of: Optional[Tensor] = None,
+                counts: Optional[Tensor] = None) -> None:
+    """sr_cloud_voxel: ``points`` [n, >= 3] fp32 (contiguous rows; the first three columns are read) reduced to
+    one point per occupied voxel of edge ``voxel`` around ``origin``, in ascending key order, into
+    ``out_points`` [capacity, 3].  ``attr`` [n, >= n_attr] fp32 rides along into ``out_attr`` [capacity,
+    n_attr]; ``mask`` [n] uint8; ``weight`` [n] fp32 (mode "best"); ``xform`` fp64 [>= 13] (scale, R, t).
+    ``out_count`` / ``out_index`` [capacity] int32, ``out_key`` [capacity] int64, ``voxel_of`` [n] int32,
+    ``counts`` [4] int32 (voxels, considered, skipped, outside): storage of the unsigned values."""
+    if mode not in VOXEL_MODE:
+        raise ValueError(f"mode must be one of {sorted(VOXEL_MODE)}, got {mode!r}")
+    n, cols, ldp = _rows(points, "points", torch.float32)
+    if cols < 3:
+        raise ValueError(f"points must be [n, >= 3], got {tuple(points.shape)}")
+    d = _lib.CloudVoxelDesc()
+    if attr is not None:
+        if _rows(attr, "attr", torch.float32)[0] != n or attr.device != points.device:
+            raise ValueError(f"attr must have {n} rows on {points.device}")
+        d.lda = attr.stride(0)
+        d.n_attr = attr.shape[1] if n_attr is None else int(n_attr)
+        if d.n_attr > attr.shape[1]:
+            raise ValueError(f"n_attr {d.n_attr} exceeds the {attr.shape[1]} columns of attr")
+    elif n_attr:
+        raise ValueError("n_attr without attr")
+    capacity = n if capacity is None else int(capacity)
+    if out_points.dim() != 2 or out_points.shape[1] != 3 or out_points.shape[0] < capacity:
+        raise ValueError(f"out_points must be [>= {capacity}, 3], got {tuple(out_points.shape)}")
+    for name, t, dt, per in (("out_points", out_points, torch.float32, 3), ("out_attr", out_attr, torch.float32, d.n_attr),
+                             ("out_count", out_count, torch.int32, 1), ("out_index", out_index, torch.int32, 1),
+                             ("out_key", out_key, torch.int64, 1)):
+        if t is not None and (t.dtype != dt or not t.is_contiguous() or t.device != points.device
+                              or t.numel() < capacity * per):
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of at least {capacity * per} entries on {points.device}")
+    _out(mask, "mask", torch.uint8, n, points)
+    _out(weight, "weight", torch.float32, n, points)
+    _out(voxel_of, "voxel_of", torch.int32, n, points)
+    _out(counts, "counts", torch.int32, 4, points)
+    if xform is not None and (xform.dtype != torch.float64 or xform.dim() != 1 or xform.numel() < 13
+                              or not xform.is_contiguous() or xform.device != points.device):
+        raise ValueError("xform must be a contiguous fp64 vector of at least 13 entries on the points' device")
+    need = cloud_voxel_workspace_bytes(n)
+    if need <= 0:
+        raise ValueError(f"{n} points are outside the downsampler's range")
+    ws = torch.empty(need, device=points.device, dtype=torch.uint8)  # stream-ordered: the caching allocator's rule
+    d.points, d.attr, d.mask, d.weight, d.xform = _p(points), _p(attr), _p(mask), _p(weight), _p(xform)
+    d.n, d.ldp, d.axis_bits, d.mode = n, ldp, int(axis_bits), VOXEL_MODE[mode]
+    d.origin[0], d.origin[1], d.origin[2] = (float(o) for o in origin)
+    d.voxel, d.capacity = float(voxel), capacity
+    d.out_points, d.out_attr, d.out_count, d.out_index = _p(out_points), _p(out_attr), _p(out_count), _p(out_index)
+    d.out_key, d.voxel_of, d.counts = _p(out_key), _p(voxel_of), _p(counts)
+    d.workspace, d.workspace_bytes = _p(ws), need
+    check(_lib.load().sr_cloud_voxel(_stream(points), ctypes.byref(d)), "sr_cloud_voxel")
+
+
 # ---------------------------------------------------------------- training step (SURVEY §8(f) rank 4)
 _TRAIN_WS = {}  # ((device, stream), name) -> fp32 workspace
 

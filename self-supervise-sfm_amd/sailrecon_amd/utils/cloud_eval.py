@@ -13,6 +13,10 @@ reconstruction papers report after a similarity alignment.
     evaluate_reconstruction  the same for the per-view dicts SailRecon.forward / reloc return, aligned
                              to ground-truth poses by sr_pose_align without leaving the device
 
+With ``voxel`` both clouds are first reduced to one point per voxel (cloud_export.voxel_downsample), the
+usual protocol of accuracy / completeness, which also makes whole scenes affordable for the brute-force
+search.
+
 accuracy is the distance pred -> gt, completeness gt -> pred; precision@t / recall@t are the fractions
 of all predicted / ground-truth points closer than t.  The nearest neighbour is found by brute force
 from direct coordinate differences in fp32, so a cloud far from the origin keeps its digits.  There is
@@ -169,25 +173,48 @@ def _one_copy(hist: Tensor, stats: Tensor, extra: Optional[Tensor] = None):
     return host[:nh].astype(np.int64).reshape(hist.shape), host[nh:nh + 12].reshape(2, 6), host[nh + 12:]
 
 
+def _voxel_pair(p: Tensor, g: Tensor, xform: Optional[Tensor], voxel: float):
+    """Both clouds reduced to the mean point of every occupied voxel of edge ``voxel``: the ground truth in its
+    frame, the prediction after ``xform`` (applied inside the kernel, so a device fit stays where it is)."""
+    from .cloud_export import voxel_downsample
+    if not (np.isfinite(voxel) and voxel > 0):
+        raise ValueError(f"voxel must be positive and finite, got {voxel!r}")
+    pv, gv = voxel_downsample(p, voxel, xform=xform), voxel_downsample(g, voxel)
+    if pv["n_voxels"] == 0 or gv["n_voxels"] == 0:
+        raise ValueError(f"no point left after downsampling at {voxel}: {pv['n_voxels']} predicted, "
+                         f"{gv['n_voxels']} ground-truth voxels")
+    return pv["points"], gv["points"]
+
+
 def cloud_accuracy(pred_points, gt_points, thresholds: Sequence[float] = (0.01, 0.02, 0.05), bin_len: float = 0.001,
-                   n_bins: int = 1024, xform=None, pred_valid=None, gt_valid=None) -> dict:
+                   n_bins: int = 1024, xform=None, pred_valid=None, gt_valid=None, voxel: Optional[float] = None) -> dict:
     """scores_from_hists of pred -> gt (accuracy) and gt -> pred (completeness).  Points are [..., 3]
     tensors or arrays (host inputs are uploaded), ``pred_valid`` / ``gt_valid`` optional bool masks of
     their leading shape.  ``xform`` (scale, R, t), or an fp64 vector holding them in that order, maps
-    the predicted cloud into the ground-truth frame inside the kernel."""
+    the predicted cloud into the ground-truth frame inside the kernel.  With ``voxel`` the ground-truth cloud
+    is downsampled at that edge in its frame and the predicted one after ``xform``, the two reduced clouds
+    are scored with no further transform, and the result gains ``n_pred_voxels`` and ``n_gt_voxels``."""
     _check_bins(bin_len, n_bins)
     _threshold_bins(thresholds, bin_len, n_bins)
     p, g = _as_points(pred_points, "pred_points", pred_valid), _as_points(gt_points, "gt_points", gt_valid)
     dev = _device_of(pred_points, gt_points, xform)
-    hist, stats = _accuracy_device(_upload(p, dev), _upload(g, dev), _as_xform(xform, dev, "xform"), n_bins, float(bin_len))
+    p, g, xf = _upload(p, dev), _upload(g, dev), _as_xform(xform, dev, "xform")
+    if voxel is not None:
+        p, g = _voxel_pair(p, g, xf, voxel)
+        xf = None
+    hist, stats = _accuracy_device(p, g, xf, n_bins, float(bin_len))
     h, s, _ = _one_copy(hist, stats)
-    return scores_from_hists(h[0], h[1], s[0], s[1], tuple(thresholds), float(bin_len))
+    res = scores_from_hists(h[0], h[1], s[0], s[1], tuple(thresholds), float(bin_len))
+    if voxel is not None:
+        res.update(n_pred_voxels=p.shape[0], n_gt_voxels=g.shape[0])
+    return res
 
 
 def evaluate_reconstruction(predictions, gt_points, gt_poses=None, key: str = "point_map_by_unprojection",
                             conf_key: Optional[str] = None, conf_thresh: Optional[float] = None,
                             with_scale: bool = True, thresholds: Sequence[float] = (0.01, 0.02, 0.05),
-                            bin_len: float = 0.001, n_bins: int = 1024, gt_valid=None) -> dict:
+                            bin_len: float = 0.001, n_bins: int = 1024, gt_valid=None,
+                            voxel: Optional[float] = None) -> dict:
     """cloud_accuracy of the points of ``predictions`` (the list of per-view dicts SailRecon.forward and
     reloc return) against ``gt_points``.  The points come from ``key`` ("point_map_by_unprojection", or
     "point_map" with ``conf_key="xyz_cnf"``), kept where ``conf_key`` exceeds ``conf_thresh`` when both
@@ -196,7 +223,10 @@ def evaluate_reconstruction(predictions, gt_points, gt_poses=None, key: str = "p
     the predictions' extrinsics, and the fit goes to the kernel as it lies on the device.  The result
     then also carries ``scale``, ``R``, ``t``, ``ate`` and ``status``.  A ``status`` with bit 1 (value 2)
     set means the centres are collinear or coincident and the rotation is NOT unique (two views always
-    are): the scores then describe one of many equally good alignments; it is returned, not hidden."""
+    are): the scores then describe one of many equally good alignments; it is returned, not hidden.
+    With ``voxel`` both clouds are downsampled as in cloud_accuracy, the predicted one after the fit, which
+    goes to the downsampling kernel as it lies on the device; the result gains ``n_pred_voxels`` and
+    ``n_gt_voxels``."""
     _check_bins(bin_len, n_bins)
     _threshold_bins(thresholds, bin_len, n_bins)
     if not (isinstance(predictions, (list, tuple)) and predictions and isinstance(predictions[0], dict)):
@@ -228,10 +258,16 @@ def evaluate_reconstruction(predictions, gt_points, gt_poses=None, key: str = "p
         fit = torch.empty(14, device=dev, dtype=torch.float64)
         status = torch.empty(1, device=dev, dtype=torch.int32)
         ops.pose_align(_upload(pp, dev), _upload(gp, dev), fit, status, with_scale=with_scale)
-    hist, stats = _accuracy_device(p, g, fit, n_bins, float(bin_len))
+    if voxel is None:
+        hist, stats = _accuracy_device(p, g, fit, n_bins, float(bin_len))
+    else:
+        p, g = _voxel_pair(p, g, fit, voxel)
+        hist, stats = _accuracy_device(p, g, None, n_bins, float(bin_len))
     extra = None if fit is None else torch.cat([fit, status.to(torch.float64)])
     h, s, e = _one_copy(hist, stats, extra)
     res = scores_from_hists(h[0], h[1], s[0], s[1], tuple(thresholds), float(bin_len))
+    if voxel is not None:
+        res.update(n_pred_voxels=p.shape[0], n_gt_voxels=g.shape[0])
     if fit is not None:
         res.update(scale=float(e[0]), R=e[1:10].reshape(3, 3).copy(), t=e[10:13].copy(), ate=float(e[13]),
                    status=int(e[14]))

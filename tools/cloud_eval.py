@@ -3,7 +3,7 @@
 and precision / recall / F-score at distance thresholds.
 
     python tools/cloud_eval.py PRED.ply GT.ply [--pred-poses P.txt --gt-poses G.txt] [--no-scale]
-                               [--thresholds 0.01 0.02 0.05] [--bin-len 0.001]
+                               [--thresholds 0.01 0.02 0.05] [--bin-len 0.001] [--voxel 0.01]
 
 The PLY files are read by the small reader below (``binary_little_endian`` and ``ascii``; the ``x y z``
 properties of the ``vertex`` element, whatever else it carries), which reads what ``save_pointcloud_ply``
@@ -11,6 +11,8 @@ of tools/demo_imc_forward.py writes (the reference's pred.ply, train/train_imc.p
 two KITTI pose files (tools/pose_eval.py) the predicted cloud is first brought into the ground-truth
 frame by the similarity fit of the camera centres, which stays on the device.  The scores come from
 ``sailrecon_amd.utils.cloud_eval``, which runs on the device; one JSON line of the result is printed.
+With ``--voxel V`` both clouds are first reduced to one point per voxel of edge V (the ground truth in
+its frame, the prediction after the fit), as the published accuracy / completeness protocols do.
 """
 
 from __future__ import annotations
@@ -88,7 +90,7 @@ def read_ply_xyz(path: str) -> np.ndarray:
         return out
 
 
-def main(argv=None) -> dict:
+def parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("pred", help="predicted cloud, PLY")
     ap.add_argument("gt", help="ground-truth cloud, PLY")
@@ -98,12 +100,20 @@ def main(argv=None) -> dict:
     ap.add_argument("--thresholds", type=float, nargs="+", default=[0.01, 0.02, 0.05], help="distances")
     ap.add_argument("--bin-len", type=float, default=0.001, help="histogram bin; thresholds are multiples of it")
     ap.add_argument("--bins", type=int, default=1024)
+    ap.add_argument("--voxel", type=float, default=None, help="downsample both clouds to voxels of this edge first")
+    return ap
+
+
+def main(argv=None) -> dict:
+    ap = parser()
     a = ap.parse_args(argv)
     if (a.pred_poses is None) != (a.gt_poses is None):
         ap.error("--pred-poses and --gt-poses go together")
+    if a.voxel is not None and not (np.isfinite(a.voxel) and a.voxel > 0):
+        ap.error("--voxel must be positive and finite")
     from sailrecon_amd.utils.cloud_eval import cloud_accuracy, evaluate_reconstruction
     pred, gt = read_ply_xyz(a.pred), read_ply_xyz(a.gt)
-    kw = dict(thresholds=tuple(a.thresholds), bin_len=a.bin_len, n_bins=a.bins)
+    kw = dict(thresholds=tuple(a.thresholds), bin_len=a.bin_len, n_bins=a.bins, voxel=a.voxel)
     if a.pred_poses is None:
         res = cloud_accuracy(pred, gt, **kw)
     else:

@@ -19,8 +19,15 @@ Flow, step for step with the reference:
      [extrinsic; 0 0 0 1], first three rows per line) and ``scene_info.txt``.  The ``eval`` package
      is absent from the reference, so the two writers are restated here from their call sites.
 
+  6. with ``--voxel V``: additionally ``pred_filtered.ply``, the same views as one cloud from
+     ``sailrecon_amd.utils.cloud_export.scene_cloud`` -- pixels below their view's ``--conf-quantile``
+     confidence dropped, one point per voxel of edge V (the mean of its members, or with ``--voxel-mode
+     best`` its most confident one) -- and a ``Filtered Points:`` line in ``scene_info.txt``.  Without
+     the flag the three outputs are what they were.
+
     python tools/demo_imc_forward.py [--ckpt sailrecon.pt] [--images DIR] [--num-images 5]
                                      [--scenes 1] [--out gpurun_out/demo_imc]
+                                     [--voxel V [--conf-quantile Q] [--voxel-mode mean|best]]
 """
 
 from __future__ import annotations
@@ -112,7 +119,8 @@ def scene_images(images_dir: Optional[str], n: int, scene_idx: int, img_size: in
 
 def demo(ckpt: Optional[str] = None, images_dir: Optional[str] = None, num_images: int = 5, max_scenes: int = 1,
          out_dir: str = "gpurun_out/demo_imc", img_size: int = 518, model: Optional[SailRecon] = None,
-         verbose: bool = True) -> List[List[Dict]]:
+         verbose: bool = True, voxel: Optional[float] = None, conf_quantile: float = 0.0,
+         voxel_mode: str = "mean") -> List[List[Dict]]:
     device = "cuda"
     if not torch.cuda.is_available():
         raise RuntimeError("demo_imc_forward runs on the HIP path (no ROCm device visible)")
@@ -142,6 +150,11 @@ def demo(ckpt: Optional[str] = None, images_dir: Optional[str] = None, num_image
         w2c = [p["extrinsic"][0].float().numpy() for p in predictions]    # :118-120
         c2w = [np.linalg.inv(np.vstack([T, np.array([0, 0, 0, 1])])) for T in w2c]  # :121-124
         save_kitti_poses(c2w, os.path.join(out, "pred.txt"))              # :126-128
+        n_filtered = None
+        if voxel is not None:
+            from sailrecon_amd.utils.cloud_export import save_ply, scene_cloud
+            cloud = scene_cloud(predictions, conf_quantile=conf_quantile, voxel=voxel, mode=voxel_mode)
+            n_filtered = save_ply(os.path.join(out, "pred_filtered.ply"), cloud["points"], cloud["colors"])
         with open(os.path.join(out, "scene_info.txt"), "w") as f:         # :131-138
             f.write(f"Scene Name: {scene_name}\n")
             f.write(f"Number of Images: {n}\n")
@@ -149,12 +162,15 @@ def demo(ckpt: Optional[str] = None, images_dir: Optional[str] = None, num_image
             f.write("Correspondence Pairs: []\n")
             f.write(f"Images Tensor Shape: {tuple(images.shape)}\n")
             f.write(f"Number of Predictions: {len(predictions)}\n")
+            if n_filtered is not None:
+                f.write(f"Filtered Points: {n_filtered} (voxel {voxel:g}, conf quantile {conf_quantile:g}, "
+                        f"{voxel_mode})\n")
         log(f"saved {nv} points, {len(c2w)} poses and the scene info under {out}")
         results.append(predictions)
     return results
 
 
-def main(argv=None):
+def parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--ckpt", default=None, help="local SailRecon state_dict (.pt), loaded weights_only")
     ap.add_argument("--images", default=None, help="directory of scene images (N per scene, sorted)")
@@ -162,8 +178,25 @@ def main(argv=None):
     ap.add_argument("--scenes", type=int, default=1)
     ap.add_argument("--img-size", type=int, default=518)
     ap.add_argument("--out", default="gpurun_out/demo_imc")
+    ap.add_argument("--voxel", type=float, default=None, help="also write pred_filtered.ply, one point per voxel of this edge")
+    ap.add_argument("--conf-quantile", type=float, default=0.0,
+                    help="with --voxel: drop the pixels below this quantile of their view's confidence")
+    ap.add_argument("--voxel-mode", choices=("mean", "best"), default="mean",
+                    help="with --voxel: a voxel's mean point, or its most confident member")
+    return ap
+
+
+def main(argv=None):
+    ap = parser()
     a = ap.parse_args(argv)
-    demo(a.ckpt, a.images, a.num_images, a.scenes, a.out, a.img_size)
+    if a.voxel is None and (a.conf_quantile != 0.0 or a.voxel_mode != "mean"):
+        ap.error("--conf-quantile and --voxel-mode go with --voxel")
+    if a.voxel is not None and not (np.isfinite(a.voxel) and a.voxel > 0):
+        ap.error("--voxel must be positive and finite")
+    if not 0.0 <= a.conf_quantile <= 1.0:
+        ap.error("--conf-quantile must be in [0, 1]")
+    demo(a.ckpt, a.images, a.num_images, a.scenes, a.out, a.img_size, voxel=a.voxel, conf_quantile=a.conf_quantile,
+         voxel_mode=a.voxel_mode)
 
 
 if __name__ == "__main__":

@@ -1052,6 +1052,109 @@ def depth(runs=3):
         del gt, p, m
 
 
+def voxel(runs=3):
+    """The stable radix sort and the voxel downsampling (sr_sort_pairs, sr_cloud_voxel) against their torch
+    statements, in alternation in one process, ``runs`` timed runs each after one warm-up, HIP events, each
+    side ending in its D2H copy.
+      sort      sr_sort_pairs (keys and permutation out) against torch.sort(stable=True) on int64, n = 5 and
+                32 x 518^2, key_bits 31 and 64.  GB/s per pass = 32 bytes per element (the histogram reads
+                the key, the scatter reads key and value and writes both) over the time of one pass, beside
+                the 6.3 TB/s a streaming kernel reaches on this part (MI355X_MICROARCH "HBM").
+      voxel     cloud_export.voxel_downsample (mean, r g b conf attributes) on a synthetic 32-view scene
+                (32 x 518^2 points uniform in the unit cube) at edges giving about 1, 10 and 100 members per
+                voxel, against torch.unique(keys, return_inverse, return_counts) + an fp64 index_add_.
+      eval      cloud_eval.evaluate_reconstruction with voxel= against the same call without it, 2^20
+                predicted against 2^20 ground-truth points (the size at which brute force still finishes)."""
+    from sailrecon_amd.utils.cloud_eval import evaluate_reconstruction
+    from sailrecon_amd.utils.cloud_export import voxel_downsample
+    g = torch.Generator(device=DEV).manual_seed(0)
+
+    def alternate(fns, label, note=lambda name, best: ""):
+        times = {k: [] for k in fns}
+        for fn in fns.values():
+            fn()
+        torch.cuda.synchronize()
+        for _ in range(runs):
+            for name, fn in fns.items():
+                times[name].append(timeit(fn, reps=1, warm=0))
+        for name, ms in times.items():
+            print(f"{label} {name:24s}: " + " ".join(f"{t:9.3f}" for t in ms) + f" ms  best {min(ms):9.3f} ms" +
+                  note(name, min(ms)), flush=True)
+        return {k: min(v) for k, v in times.items()}
+
+    for views in (5, 32):
+        n = views * 518 * 518
+        for bits in (31, 64):
+            # non-negative int64, so that torch's signed order is the unsigned one; under 64 bits all eight digits vary
+            keys = torch.randint(0, 2 ** 62, (n,), device=DEV, generator=g, dtype=torch.int64)
+            keys = keys * 2 + torch.randint(0, 2, (n,), device=DEV, generator=g, dtype=torch.int64) if bits == 64 else \
+                keys & (2 ** 31 - 1)
+            passes = (bits + 7) // 8
+
+            def ours():
+                sk, perm = ops.sort_pairs(keys, key_bits=bits)
+                return perm[:1].cpu()
+
+            def theirs():
+                sk, perm = torch.sort(keys, stable=True)
+                return perm[:1].cpu()
+
+            best = alternate({"sr_sort_pairs": ours, "torch.sort(stable)": theirs}, f"sort {views} x 518^2, {bits} bits",
+                             lambda name, ms: (f"  {passes} passes, {32 * n * passes / (ms * 1e-3) / 1e9:7.1f} GB/s moved "
+                                               "(HBM streaming: 6300)") if name == "sr_sort_pairs" else "")
+            same = bool(torch.equal(ops.sort_pairs(keys, key_bits=bits)[1].long(), torch.sort(keys, stable=True)[1]))
+            print(f"sort {views} x 518^2, {bits} bits: sr_sort_pairs is {best['torch.sort(stable)'] / best['sr_sort_pairs']:.2f} x "
+                  f"torch.sort's speed; same permutation: {same}  [{ops.last_kernel()}]", flush=True)
+            del keys
+    n = 32 * 518 * 518
+    p = torch.rand(n, 3, device=DEV, generator=g)
+    attrs = torch.rand(n, 4, device=DEV, generator=g)
+    for members in (1, 10, 100):
+        v = (members / n) ** (1 / 3)
+
+        def ours():
+            return voxel_downsample(p, v, attrs=attrs, axis_bits=21)["n_voxels"]
+
+        def theirs():
+            f = torch.floor(p.double() / v).long() + 2 ** 20
+            keys = (f[:, 2] << 42) | (f[:, 1] << 21) | f[:, 0]
+            uk, inv, cnt = torch.unique(keys, return_inverse=True, return_counts=True)
+            acc = torch.zeros(uk.numel(), 7, device=DEV, dtype=torch.float64)
+            acc.index_add_(0, inv, torch.cat([p, attrs], dim=1).double())
+            out = (acc / cnt[:, None]).float()
+            return int(out.shape[0]), out[:1].cpu()
+
+        best = alternate({"voxel_downsample": ours, "unique + index_add_": theirs}, f"voxel 32 x 518^2, ~{members} per voxel")
+        print(f"voxel 32 x 518^2, edge {v:.5f}: {ours()} voxels (statement {theirs()[0]}); voxel_downsample is "
+              f"{best['unique + index_add_'] / best['voxel_downsample']:.2f} x the statement's speed  [{ops.last_kernel()}]",
+              flush=True)
+    del p, attrs
+    m = 1 << 20
+    gt = torch.rand(m, 3, device=DEV, generator=g)
+    pred = [{"points": gt[k::4] + 0.002 * torch.randn(m // 4, 3, device=DEV, generator=g)} for k in range(4)]
+    res = {}
+
+    def scored(vx):
+        res[vx] = evaluate_reconstruction(pred, gt, key="points", voxel=vx)
+        return res[vx]
+
+    best = alternate({"voxel=0.02": lambda: scored(0.02), "voxel=None": lambda: scored(None)}, "eval 2^20 x 2^20")
+    print(f"eval 2^20 x 2^20: voxel=0.02 scores {res[0.02]['n_pred_voxels']} x {res[0.02]['n_gt_voxels']} voxels, chamfer "
+          f"{res[0.02]['chamfer']:.5f} against {res[None]['chamfer']:.5f} unreduced, {best['voxel=None'] / best['voxel=0.02']:.1f} x "
+          "the speed", flush=True)
+
+
+def voxel_once():
+    """One sort and one downsampling at 32 x 518^2, for a kernel trace of their own."""
+    from sailrecon_amd.utils.cloud_export import voxel_downsample
+    g = torch.Generator(device=DEV).manual_seed(0)
+    n = 32 * 518 * 518
+    p = torch.rand(n, 3, device=DEV, generator=g)
+    attrs = torch.rand(n, 4, device=DEV, generator=g)
+    for members in (1, 10, 100):
+        print(members, voxel_downsample(p, (members / n) ** (1 / 3), attrs=attrs)["n_voxels"], flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["attn", "gemm", "ln"]
     for w in which:
