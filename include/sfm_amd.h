@@ -1297,6 +1297,66 @@ int64_t sr_cloud_voxel_workspace(int64_t n);
  * aligned; an fp64 or 64-bit pointer (xform, out_key) that is not 8-byte aligned. */
 int sr_cloud_voxel(sr_stream_t stream, const sr_cloud_voxel_desc* desc);
 
+/* ------------------------------------------------------------------------------------------
+ * Sparsification curves (ABI 1.14): per group of rows, the fp64 sums of a per-element error over the K
+ * bins of two orders of the group's elements, that of a confidence and the oracle order of the error
+ * itself.  The curves, AUSE and AURG are read off the sums on the host after one D2H copy.
+ * Definitions: DESIGN.md "Scoring confidence maps", csrc/sr_sparsify.hip.
+ *   considered  an element of [0, row_len) of a row whose group lies in [0, n_groups), whose mask byte
+ *               (if a mask is given) is non-zero and whose err and conf are both finite (exponent bits
+ *               not all ones: a test on the bits, as in sr_select_ranks).  Every other element of such a
+ *               row counts as skipped.  A row whose group lies outside [0, n_groups) is ignored (nothing
+ *               is indexed through it).  Elements at row_len .. row_stride are never loaded.
+ *   flat index  i = r row_len + c
+ *   order C     a group's considered elements ascending by sr_select_ranks' key on conf, bits ^ (sign ?
+ *               0xffffffff : 0x80000000), unsigned, -0 before +0: the least confident first.  Under
+ *               SR_SPARSIFY_UNCERTAINTY the key is complemented: the largest value first.  Equal keys keep
+ *               ascending flat index in both cases.
+ *   order O     the same rule on err with the key complemented: the largest error first, ties in
+ *               ascending flat index
+ *   bins        with n the group's considered count, b_k = floor(k n / K) in 64-bit integers, k = 0 .. K;
+ *               bin_sum[g][c][k] = the fp64 sum of (double)err over the positions [b_k, b_{k+1}) of order
+ *               c (C is c = 0, O is c = 1); an empty bin gives +0
+ *   cut         cut[g][k] = the conf at position b_k of order C, by its bits (b_k < n for k < K when
+ *               n >= 1): the confidence threshold that removes the fraction b_k / n.  0x7fc00000 for n = 0.
+ *   Kernels: the keys (group << 32) | key32, sentinel group n_groups for whatever is not considered, and
+ *   the counts (ballots, integer atomics); sr_sort_pairs' passes twice on 32 + bit_length(n_groups) bits,
+ *   order C carrying the err bits as its value, order O's err read back from its sorted key; a
+ *   one-workgroup scan of the group counts; a segmented reduction, a bin of more than 4096 positions
+ *   split over several workgroups; one wave per bin summing the partials and writing cut.  Sums in a
+ *   fixed order: a lane's elements ascending, a fixed LDS tree, the partials of a bin ascending by lane
+ *   and a fixed shuffle tree.  Integer atomics only, no waiting on another workgroup: any two runs give
+ *   the same bits.  Inputs are not written.
+ * ------------------------------------------------------------------------------------------ */
+enum sr_sparsify_order { SR_SPARSIFY_CONFIDENCE = 0,   /* least confident removed first */
+                         SR_SPARSIFY_UNCERTAINTY = 1 };/* largest value removed first */
+typedef struct sr_sparsify_desc {
+  const float* err;           /* [n_rows][row_stride] fp32 per-element error */
+  const float* conf;          /* [n_rows][row_stride] fp32 */
+  const uint8_t* mask;        /* [n_rows][row_stride] bytes, 0 = skip, or NULL */
+  const int32_t* group;       /* [n_rows] in [0, n_groups), or NULL: row r is group r (n_groups == n_rows) */
+  int64_t n_rows, row_len, row_stride; /* n_rows * row_len <= 2^31 - 1 */
+  int n_groups;               /* 1 .. min(n_rows, 65535) */
+  int n_steps;                /* K: 1 .. 1024 */
+  int order;                  /* sr_sparsify_order */
+  double* bin_sum;            /* [n_groups][2][K] */
+  float* cut;                 /* [n_groups][K], or NULL */
+  uint32_t* count;            /* [n_groups][2]: considered, skipped; or NULL */
+  void* workspace;            /* >= sr_sparsify_workspace(...) bytes, 16-byte aligned, stream-ordered reuse */
+  int64_t workspace_bytes;
+} sr_sparsify_desc;
+
+/* Bytes of workspace: both key arrays, the err bits, order C's sorted keys and values, the group counts and
+ * scans, the partial sums and sr_sort_workspace(n_rows * row_len).  Never shrinks when an argument grows;
+ * 0 for arguments sr_sparsify would reject. */
+int64_t sr_sparsify_workspace(int64_t n_rows, int64_t row_len, int n_groups, int n_steps);
+/* Asynchronous and allocation-free.  SR_EINVAL for a null desc, err, conf, bin_sum or workspace; n_rows or
+ * row_len below 1; row_stride < row_len; n_rows * row_len above 2^31 - 1; n_groups outside
+ * [1, min(n_rows, 65535)]; a NULL group with n_groups != n_rows; n_steps outside [1, 1024]; an order outside
+ * sr_sparsify_order; a workspace that is too small or not 16-byte aligned; a bin_sum that is not 8-byte
+ * aligned. */
+int sr_sparsify(sr_stream_t stream, const sr_sparsify_desc* desc);
+
 #ifdef __cplusplus
 }
 #endif

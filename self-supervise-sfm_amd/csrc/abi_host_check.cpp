@@ -13,6 +13,7 @@
 //   abi_host_check layout cloud_eval   the same for sr_cloud_nn_desc (ABI 1.11)
 //   abi_host_check layout depth_eval   the same for sr_select_desc and sr_depth_eval_desc (ABI 1.12)
 //   abi_host_check layout cloud_voxel   the same for sr_sort_desc and sr_cloud_voxel_desc (ABI 1.13)
+//   abi_host_check layout sparsify   the same for sr_sparsify_desc (ABI 1.14)
 //   abi_host_check check    the validation sweep; exit 0 iff every call returned what it should
 #include <cstddef>
 #include <cstdio>
@@ -207,6 +208,18 @@ void layout_cloud_voxel() {
           FIELD(sr_cloud_voxel_desc, out_attr), FIELD(sr_cloud_voxel_desc, out_count), FIELD(sr_cloud_voxel_desc, out_index),
           FIELD(sr_cloud_voxel_desc, out_key), FIELD(sr_cloud_voxel_desc, voxel_of), FIELD(sr_cloud_voxel_desc, counts),
           FIELD(sr_cloud_voxel_desc, workspace), FIELD(sr_cloud_voxel_desc, workspace_bytes)));
+  std::printf("}\n");
+}
+
+void layout_sparsify() {
+  const char* sep = "";
+  std::printf("{");
+  STRUCT(sr_sparsify_desc,
+         (FIELD(sr_sparsify_desc, err), FIELD(sr_sparsify_desc, conf), FIELD(sr_sparsify_desc, mask),
+          FIELD(sr_sparsify_desc, group), FIELD(sr_sparsify_desc, n_rows), FIELD(sr_sparsify_desc, row_len),
+          FIELD(sr_sparsify_desc, row_stride), FIELD(sr_sparsify_desc, n_groups), FIELD(sr_sparsify_desc, n_steps),
+          FIELD(sr_sparsify_desc, order), FIELD(sr_sparsify_desc, bin_sum), FIELD(sr_sparsify_desc, cut),
+          FIELD(sr_sparsify_desc, count), FIELD(sr_sparsify_desc, workspace), FIELD(sr_sparsify_desc, workspace_bytes)));
   std::printf("}\n");
 }
 
@@ -1050,6 +1063,101 @@ void check() {
     u = vd, u.out_key = (uint64_t*)((char*)fake(9) + 4);
     expect("sr_cloud_voxel out_key % 8", sr_cloud_voxel(nullptr, &u), false);
   }
+  {
+    // ---- sr_sparsify (ABI 1.14): the workspace sweep, the planned shapes up to the launch, every rejection
+    const int64_t pix = 518LL * 518, most = 2147483647LL;
+    {  // never shrinks when an argument grows; 0 for what the call rejects
+      const int64_t rows[] = {1, 2, 3, 5, 32, 64, 65535, 70001}, lens[] = {1, 2, 63, 64, 65, 2047, 2048, 2049, 6149, 30000};
+      const int groups[] = {1, 2, 3, 5, 32, 65535}, steps[] = {1, 2, 3, 7, 100, 1024};
+      for (int64_t r : rows)
+        for (int64_t l : lens)
+          for (int g : groups)
+            for (int k : steps) {
+              if (g > r) continue;
+              const int64_t w = sr_sparsify_workspace(r, l, g, k);
+              if (w <= 0 || w % 16 || w < 32 * r * l + sr_sort_workspace(r * l) + 16 * (int64_t)g * k) ++g_fail;
+              if (sr_sparsify_workspace(r + 1, l, g, k) < w || sr_sparsify_workspace(r, l + 1, g, k) < w) ++g_fail;
+              if (g + 1 <= r && g + 1 <= 65535 && sr_sparsify_workspace(r, l, g + 1, k) < w) ++g_fail;
+              if (k + 1 <= 1024 && sr_sparsify_workspace(r, l, g, k + 1) < w) ++g_fail;
+            }
+      if (sr_sparsify_workspace(0, 5, 1, 1) || sr_sparsify_workspace(5, 0, 1, 1) || sr_sparsify_workspace(-1, 5, 1, 1) ||
+          sr_sparsify_workspace(5, 5, 0, 1) || sr_sparsify_workspace(5, 5, 6, 1) || sr_sparsify_workspace(70000, 5, 65536, 1) ||
+          sr_sparsify_workspace(5, 5, 1, 0) || sr_sparsify_workspace(5, 5, 1, 1025) || sr_sparsify_workspace(2, 1LL << 30, 1, 1) ||
+          sr_sparsify_workspace(1LL << 31, 1, 1, 1) || sr_sparsify_workspace(1LL << 62, 4, 1, 1) ||
+          sr_sparsify_workspace(most, 1, 1, 1) <= 0 || sr_sparsify_workspace(1, most, 1, 1) <= 0)
+        ++g_fail;
+      std::printf("sparsify workspace bytes at 32 x 518 x 518, K = 100, view / scene: %lld / %lld\n",
+                  (long long)sr_sparsify_workspace(32, pix, 32, 100), (long long)sr_sparsify_workspace(32, pix, 1, 100));
+    }
+    sr_sparsify_desc sd{};
+    sd.err = fake<float>(0), sd.conf = fake<float>(1), sd.mask = fake<uint8_t>(2), sd.group = fake<int32_t>(3);
+    sd.n_rows = 32, sd.row_len = pix, sd.row_stride = pix, sd.n_groups = 4, sd.n_steps = 100;
+    sd.order = SR_SPARSIFY_CONFIDENCE, sd.bin_sum = fake<double>(4), sd.cut = fake<float>(5), sd.count = fake<uint32_t>(6);
+    sd.workspace = fake(7), sd.workspace_bytes = sr_sparsify_workspace(32, pix, 4, 100);
+    expect("sr_sparsify 32 x 518 x 518 in 4 groups, every output", sr_sparsify(nullptr, &sd), true);
+    sr_sparsify_desc v = sd;
+    v = sd, v.order = SR_SPARSIFY_UNCERTAINTY, v.mask = nullptr, v.cut = nullptr, v.count = nullptr;
+    expect("sr_sparsify uncertainty, bare", sr_sparsify(nullptr, &v), true);
+    v = sd, v.group = nullptr, v.n_groups = 32, v.workspace_bytes = sr_sparsify_workspace(32, pix, 32, 100);
+    expect("sr_sparsify by view", sr_sparsify(nullptr, &v), true);
+    v = sd, v.n_groups = 1, v.row_stride = pix + 3;
+    expect("sr_sparsify by scene, padded rows", sr_sparsify(nullptr, &v), true);
+    for (int k : {1, 2, 3, 7, 1024}) {
+      v = sd, v.n_steps = k, v.workspace_bytes = sr_sparsify_workspace(32, pix, 4, k);
+      expect("sr_sparsify n_steps sweep", sr_sparsify(nullptr, &v), true);
+    }
+    for (int64_t l : {int64_t(1), int64_t(2), int64_t(255), int64_t(256), int64_t(257), int64_t(4097), int64_t(70001)}) {
+      v = sd, v.n_rows = 3, v.row_len = v.row_stride = l, v.n_groups = 3, v.group = nullptr;
+      expect("sr_sparsify row_len sweep", sr_sparsify(nullptr, &v), true);
+    }
+    v = sd, v.n_rows = 70000, v.row_len = v.row_stride = 3, v.n_groups = 65535, v.n_steps = 1024;
+    v.workspace_bytes = sr_sparsify_workspace(70000, 3, 65535, 1024);
+    expect("sr_sparsify 65535 groups of 1024 steps", sr_sparsify(nullptr, &v), true);
+    v = sd, v.n_rows = 1, v.row_len = v.row_stride = most, v.n_groups = 1, v.n_steps = 1;
+    v.workspace_bytes = sr_sparsify_workspace(1, most, 1, 1);
+    expect("sr_sparsify 2^31 - 1 elements", sr_sparsify(nullptr, &v), true);
+    expect("sr_sparsify null desc", sr_sparsify(nullptr, nullptr), false);
+    v = sd, v.err = nullptr;
+    expect("sr_sparsify null err", sr_sparsify(nullptr, &v), false);
+    v = sd, v.conf = nullptr;
+    expect("sr_sparsify null conf", sr_sparsify(nullptr, &v), false);
+    v = sd, v.bin_sum = nullptr;
+    expect("sr_sparsify null bin_sum", sr_sparsify(nullptr, &v), false);
+    v = sd, v.workspace = nullptr;
+    expect("sr_sparsify null workspace", sr_sparsify(nullptr, &v), false);
+    v = sd, v.n_rows = 0;
+    expect("sr_sparsify n_rows 0", sr_sparsify(nullptr, &v), false);
+    v = sd, v.row_len = 0, v.row_stride = 0;
+    expect("sr_sparsify row_len 0", sr_sparsify(nullptr, &v), false);
+    v = sd, v.row_stride = pix - 1;
+    expect("sr_sparsify row_stride < row_len", sr_sparsify(nullptr, &v), false);
+    v = sd, v.n_rows = 8004, v.workspace_bytes = int64_t(1) << 50;
+    expect("sr_sparsify 2^31 elements and more", sr_sparsify(nullptr, &v), false);
+    v = sd, v.n_rows = int64_t(1) << 62, v.row_len = v.row_stride = 4, v.workspace_bytes = int64_t(1) << 50;
+    expect("sr_sparsify a product that overflows", sr_sparsify(nullptr, &v), false);
+    v = sd, v.n_groups = 0;
+    expect("sr_sparsify n_groups 0", sr_sparsify(nullptr, &v), false);
+    v = sd, v.n_groups = 33;
+    expect("sr_sparsify n_groups above n_rows", sr_sparsify(nullptr, &v), false);
+    v = sd, v.n_rows = 70000, v.row_len = v.row_stride = 3, v.n_groups = 65536, v.workspace_bytes = int64_t(1) << 50;
+    expect("sr_sparsify n_groups 65536", sr_sparsify(nullptr, &v), false);
+    v = sd, v.group = nullptr;
+    expect("sr_sparsify no group, n_groups != n_rows", sr_sparsify(nullptr, &v), false);
+    v = sd, v.n_steps = 0;
+    expect("sr_sparsify n_steps 0", sr_sparsify(nullptr, &v), false);
+    v = sd, v.n_steps = 1025, v.workspace_bytes = int64_t(1) << 50;
+    expect("sr_sparsify n_steps 1025", sr_sparsify(nullptr, &v), false);
+    v = sd, v.order = 2;
+    expect("sr_sparsify order 2", sr_sparsify(nullptr, &v), false);
+    v = sd, v.order = -1;
+    expect("sr_sparsify order -1", sr_sparsify(nullptr, &v), false);
+    v = sd, v.workspace_bytes -= 1;
+    expect("sr_sparsify workspace one byte short", sr_sparsify(nullptr, &v), false);
+    v = sd, v.workspace = (char*)fake(7) + 8;
+    expect("sr_sparsify workspace % 16", sr_sparsify(nullptr, &v), false);
+    v = sd, v.bin_sum = (double*)((char*)fake(4) + 4);
+    expect("sr_sparsify bin_sum % 8", sr_sparsify(nullptr, &v), false);
+  }
   expect("sr_pose_decode_f32 null", sr_pose_decode_f32(nullptr, nullptr, 9, 0, 518, 518, nullptr, nullptr), false);
   expect("sr_copy_rows_f32 null", sr_copy_rows_f32(nullptr, nullptr, 0, nullptr, 0, nullptr, 0, 0), false);
   expect("sr_conv3x3_f32 null", sr_conv3x3_f32(nullptr, nullptr, 1, 8, 8, 32, 1, 0, nullptr, 32, SR_EPI_BIAS, &ep, nullptr, 32, nullptr), false);
@@ -1129,6 +1237,8 @@ int main(int argc, char** argv) {
       layout_depth_eval();
     else if (argc > 2 && std::string(argv[2]) == "cloud_voxel")
       layout_cloud_voxel();
+    else if (argc > 2 && std::string(argv[2]) == "sparsify")
+      layout_sparsify();
     else
       layout();
     return 0;

@@ -218,6 +218,18 @@ class CloudVoxelDesc(ctypes.Structure):
     ]
 
 
+SR_SPARSIFY_CONFIDENCE, SR_SPARSIFY_UNCERTAINTY = 0, 1
+
+
+class SparsifyDesc(ctypes.Structure):
+    """sr_sparsify_desc (include/sfm_amd.h)."""
+    _fields_ = [
+        ("err", _vp), ("conf", _vp), ("mask", _vp), ("group", _vp), ("n_rows", _i64), ("row_len", _i64),
+        ("row_stride", _i64), ("n_groups", _i32), ("n_steps", _i32), ("order", _i32), ("bin_sum", _vp), ("cut", _vp),
+        ("count", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
+    ]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "sr_last_error": (ctypes.c_char_p, []),
@@ -327,6 +339,8 @@ _PROTOS = {
     "sr_sort_pairs": (_i32, [_vp, ctypes.POINTER(SortDesc)]),
     "sr_cloud_voxel_workspace": (_i64, [_i64]),
     "sr_cloud_voxel": (_i32, [_vp, ctypes.POINTER(CloudVoxelDesc)]),
+    "sr_sparsify_workspace": (_i64, [_i64, _i64, _i32, _i32]),
+    "sr_sparsify": (_i32, [_vp, ctypes.POINTER(SparsifyDesc)]),
 }
 EXPORTED = tuple(_PROTOS)
 

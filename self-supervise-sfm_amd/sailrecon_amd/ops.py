@@ -1676,6 +1676,46 @@ def cloud_voxel(points: Tensor, voxel: float, out_points: Tensor, *, attr: Optio
     check(_lib.load().sr_cloud_voxel(_stream(points), ctypes.byref(d)), "sr_cloud_voxel")
 
 
+# ---------------------------------------------------------------- sparsification curves (utils/conf_eval.py)
+SPARSIFY_ORDER = {"confidence": _lib.SR_SPARSIFY_CONFIDENCE, "uncertainty": _lib.SR_SPARSIFY_UNCERTAINTY}
+
+
+def sparsify_workspace_bytes(n_rows: int, row_len: int, n_groups: int, n_steps: int) -> int:
+    """sr_sparsify_workspace (0 for arguments sr_sparsify rejects)."""
+    return int(_lib.load().sr_sparsify_workspace(int(n_rows), int(row_len), int(n_groups), int(n_steps)))
+
+
+def sparsify(err: Tensor, conf: Tensor, n_steps: int, bin_sum: Tensor, *, mask: Optional[Tensor] = None,
+             group: Optional[Tensor] = None, n_groups: Optional[int] = None, order: str = "confidence",
+             cut: Optional[Tensor] = None, count: Optional[Tensor] = None) -> None:
+    """sr_sparsify: for every group of rows of ``err`` / ``conf`` [rows, length] fp32 (same shape and row
+    stride; row r is group ``group[r]``, or group r) the fp64 sums of ``err`` over the ``n_steps`` bins of the
+    confidence order and of the oracle order of its finite elements whose ``mask`` byte (uint8) is non-zero,
+    into ``bin_sum`` [n_groups, 2, n_steps] fp64; if given, ``cut`` [n_groups, n_steps] fp32 (the confidence
+    at every bin's first position) and ``count`` [n_groups, 2] int32 (considered, skipped).  ``order``
+    "confidence" removes the smallest ``conf`` first, "uncertainty" the largest."""
+    if order not in SPARSIFY_ORDER:
+        raise ValueError(f"order must be one of {sorted(SPARSIFY_ORDER)}, got {order!r}")
+    d = _lib.SparsifyDesc()
+    n_rows, row_len, stride = _rows(err, "err", torch.float32)
+    _like_rows(conf, "conf", torch.float32, err)
+    _like_rows(mask, "mask", torch.uint8, err)
+    ng = _groups(group, n_groups, n_rows, err)
+    K = int(n_steps)
+    _out(bin_sum, "bin_sum", torch.float64, ng * 2 * K, err)
+    _out(cut, "cut", torch.float32, ng * K, err)
+    _out(count, "count", torch.int32, ng * 2, err)
+    need = sparsify_workspace_bytes(n_rows, row_len, ng, K)
+    if need <= 0:
+        raise ValueError(f"{n_rows} rows of {row_len} elements in {ng} groups with {K} steps are outside the ranges")
+    ws = torch.empty(need, device=err.device, dtype=torch.uint8)  # stream-ordered: the caching allocator's rule
+    d.err, d.conf, d.mask, d.group = _p(err), _p(conf), _p(mask), _p(group)
+    d.n_rows, d.row_len, d.row_stride, d.n_groups, d.n_steps, d.order = n_rows, row_len, stride, ng, K, SPARSIFY_ORDER[order]
+    d.bin_sum, d.cut, d.count = _p(bin_sum), _p(cut), _p(count)
+    d.workspace, d.workspace_bytes = _p(ws), need
+    check(_lib.load().sr_sparsify(_stream(err), ctypes.byref(d)), "sr_sparsify")
+
+
 # ---------------------------------------------------------------- training step (SURVEY §8(f) rank 4)
 _TRAIN_WS = {}  # ((device, stream), name) -> fp32 workspace
 

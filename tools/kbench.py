@@ -1155,6 +1155,95 @@ def voxel_once():
         print(members, voxel_downsample(p, (members / n) ** (1 / 3), attrs=attrs)["n_voxels"], flush=True)
 
 
+def _sparsify_inputs(views):
+    """A heteroscedastic error with a half-informative confidence, [views, 518^2] fp32."""
+    g = torch.Generator(device=DEV).manual_seed(0)
+    sigma = torch.exp(0.75 * torch.randn(views, 518 * 518, device=DEV, generator=g))
+    err = (torch.randn(views, 518 * 518, device=DEV, generator=g) * sigma).abs()
+    conf = 1.0 / sigma + torch.rand(views, 518 * 518, device=DEV, generator=g)
+    return err, conf
+
+
+def sparsify(runs=3):
+    """The sparsification sums (sr_sparsify) against their torch statement, in alternation in one process,
+    ``runs`` timed runs each after one warm-up, HIP events, each side ending in its D2H copy of the
+    [n_groups, 2, K] bin sums.  5 and 32 x 518^2 elements, K = 100, one group per view and one for the scene.
+    The statement: the same 64-bit keys, torch.sort(stable=True) of each order, the errors gathered through the
+    permutation, an fp64 cumsum and reads at the bin boundaries."""
+    K = 100
+
+    def alternate(fns, label):
+        times = {k: [] for k in fns}
+        for fn in fns.values():
+            fn()
+        torch.cuda.synchronize()
+        for _ in range(runs):
+            for name, fn in fns.items():
+                times[name].append(timeit(fn, reps=1, warm=0))
+        for name, ms in times.items():
+            print(f"{label} {name:24s}: " + " ".join(f"{t:9.3f}" for t in ms) + f" ms  best {min(ms):9.3f} ms", flush=True)
+        return {k: min(v) for k, v in times.items()}
+
+    def key32(x):
+        b = x.view(torch.int32).long() & 0xFFFFFFFF
+        return b ^ torch.where(b >> 31 != 0, 0xFFFFFFFF, 0x80000000)
+
+    for views in (5, 32):
+        err, conf = _sparsify_inputs(views)
+        for scope in ("view", "scene"):
+            G = views if scope == "view" else 1
+            grp = None if scope == "view" else torch.zeros(views, device=DEV, dtype=torch.int32)
+            gid = (torch.arange(views, device=DEV) if scope == "view" else torch.zeros(views, device=DEV, dtype=torch.int64))
+            gid = gid[:, None].expand(views, 518 * 518).reshape(-1)
+            bin_sum = torch.empty(G, 2, K, device=DEV, dtype=torch.float64)
+            cut = torch.empty(G, K, device=DEV, dtype=torch.float32)
+            count = torch.empty(G, 2, device=DEV, dtype=torch.int32)
+
+            def ours():
+                ops.sparsify(err, conf, K, bin_sum, group=grp, n_groups=G, cut=cut, count=count)
+                return bin_sum.cpu()
+
+            def theirs():
+                e, c = err.reshape(-1), conf.reshape(-1)
+                ok = torch.isfinite(e) & torch.isfinite(c)
+                kc = torch.where(ok, (gid << 32) | key32(c), G << 32)
+                ko = torch.where(ok, (gid << 32) | (key32(e) ^ 0xFFFFFFFF), G << 32)
+                cnt = torch.bincount(gid[ok], minlength=G)
+                start = torch.cumsum(cnt, 0) - cnt
+                b = start[:, None] + (torch.arange(K + 1, device=DEV)[None] * cnt[:, None]) // K
+                sums = []
+                for keys in (kc, ko):
+                    perm = torch.sort(keys, stable=True)[1]
+                    cs = torch.cat([torch.zeros(1, device=DEV, dtype=torch.float64), torch.cumsum(e[perm].double(), 0)])
+                    sums.append(cs[b[:, 1:]] - cs[b[:, :-1]])
+                return torch.stack(sums, 1).cpu()
+
+            label = f"sparsify {views} x 518^2, K {K}, scope {scope}"
+            best = alternate({"sr_sparsify": ours, "sort + cumsum": theirs}, label)
+            a, t = ours(), theirs()
+            print(f"{label}: sr_sparsify is {best['sort + cumsum'] / best['sr_sparsify']:.2f} x the statement's speed; "
+                  f"largest relative difference of a bin sum {float(((a - t).abs() / t.abs()).max()):.2e}; workspace "
+                  f"{ops.sparsify_workspace_bytes(views, 518 * 518, G, K) / 2 ** 20:.0f} MiB  [{ops.last_kernel()}]", flush=True)
+        del err, conf
+
+
+def sparsify_once(scopes=("view", "scene")):
+    """One sr_sparsify at 32 x 518^2, K = 100, per scope, for a kernel trace of its own."""
+    from sailrecon_amd.utils.conf_eval import sparsification_curves
+    err, conf = _sparsify_inputs(32)
+    for scope in scopes:
+        r = sparsification_curves(err, conf, n_steps=100, group=scope)
+        print(scope, r["ause"][:2], r["aurg"][:2], flush=True)
+
+
+def sparsify_once_view():
+    sparsify_once(("view",))
+
+
+def sparsify_once_scene():
+    sparsify_once(("scene",))
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["attn", "gemm", "ln"]
     for w in which:
