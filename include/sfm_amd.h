@@ -1357,6 +1357,78 @@ int64_t sr_sparsify_workspace(int64_t n_rows, int64_t row_len, int n_groups, int
  * aligned. */
 int sr_sparsify(sr_stream_t stream, const sr_sparsify_desc* desc);
 
+/* ------------------------------------------------------------------------------------------
+ * Rendering a point cloud into camera views (ABI 1.15): n points and V cameras in, per camera one
+ * z-buffered depth image, one index image and optional attribute images out.  Defined to the bit.
+ * Definitions: DESIGN.md "Rendering point clouds", csrc/sr_cloud_render.hip.
+ *   skipped     (for view v) the mask byte is 0; a coordinate is non-finite (a test on the bits); the
+ *               transformed point is non-finite; view_id and exclude are both given and
+ *               view_id[i] == exclude[v]
+ *   transform   q = p without xform, else fl32(s (R p) + t) by sr_cloud_nn's rule: fp64, left to right,
+ *               nothing contracted, rounded once
+ *   camera      E = extrinsic[v], fp32 [3][4], camera from world, OpenCV, as sr_unproject_depth_f32 reads
+ *               it, every entry widened exactly.  In fp64, nothing contracted:
+ *               c_r = ((E[r][0] q_x + E[r][1] q_y) + E[r][2] q_z) + E[r][3]
+ *   clipped     a c_r is non-finite (on the bits), or c_z < z_near, or c_z > z_far, compared in fp64
+ *   pixel       u = fx (c_x / c_z) + cx, v = fy (c_y / c_z) + cy, true fp64 divisions; fx, fy, cx, cy are
+ *               K[0][0], K[1][1], K[0][2], K[1][2] of the fp32 intrinsic[v] (no other entry is read: zero
+ *               skew).  ix = floor(u + 0.5), iy = floor(v + 0.5): pixel centres lie at integers.
+ *   outside     not (0 <= ix < W and 0 <= iy < H), compared in fp64 before any conversion to an integer.
+ *               Every other point that is neither skipped nor clipped is drawn.
+ *   footprint   the (2 radius + 1)^2 pixels around (ix, iy); those outside the frame are dropped
+ *   z-buffer    key = (bits(fl32(c_z)) << 32) | i; a pixel keeps the minimum key of all points whose
+ *               footprint covers it: the nearest point, equal fp32 depths going to the lowest index.  The
+ *               empty key is all ones; no drawn point produces it.
+ *   depth       the winner's fl32(c_z); 0x7fc00000 for an empty pixel (sr_depth_eval's invalid pixel)
+ *   index       the winner's i; -1 for an empty pixel
+ *   out_attr    the winner's attribute row, bit for bit; attr_fill for an empty pixel
+ *   counts      per view: covered pixels, drawn, clipped, outside; skipped = n - drawn - clipped - outside
+ *   Kernels: a clear of the key image and the counts (16-byte stores); a draw on a grid of (point tiles,
+ *   views), per footprint pixel an ordinary load of its key and, unless that is already <= the lane's, one
+ *   64-bit unsigned atomic minimum, the three counts by ballots into one of 64 slots per view; a resolve
+ *   with one lane per pixel, which also sums the slots.  Integer atomics only, no waiting on another workgroup, and a minimum does
+ *   not depend on arrival order: any two runs give the same bits.  Inputs are not written.
+ * ------------------------------------------------------------------------------------------ */
+#define SR_RENDER_MAX_ATTR 8
+#define SR_RENDER_MAX_RADIUS 3
+typedef struct sr_cloud_render_desc {
+  const float* points;        /* [n][ldp] fp32 */
+  const float* attr;          /* [n][lda] fp32, or NULL (n_attr == 0) */
+  const uint8_t* mask;        /* [n] bytes, 0 = skip, or NULL */
+  const int32_t* view_id;     /* [n] the view a point came from, or NULL; given together with exclude */
+  const int32_t* exclude;     /* [n_views] the view_id that view v does not draw, or NULL */
+  const double* xform;        /* device [13]: scale, R row-major, t -- sr_pose_align's out[0..12] -- or NULL */
+  const float* extrinsic;     /* [n_views][3][4] fp32, camera from world */
+  const float* intrinsic;     /* [n_views][3][3] fp32 */
+  int64_t n;                  /* 1 .. 2^31 - 1 */
+  int64_t ldp;                /* floats between points, >= 3 */
+  int64_t lda;                /* floats between attribute rows, >= n_attr */
+  int n_attr;                 /* 0 .. SR_RENDER_MAX_ATTR columns used */
+  int n_views;                /* V: 1 .. 65535 */
+  int height, width;          /* H, W >= 1; V H W <= 2^31 - 1 */
+  int radius;                 /* 0 .. SR_RENDER_MAX_RADIUS */
+  double z_near;              /* finite, > 0 */
+  double z_far;               /* >= z_near, may be +Inf */
+  float attr_fill;            /* out_attr of an empty pixel, by its bits */
+  float* depth;               /* [V][H][W], or NULL */
+  int32_t* index;             /* [V][H][W], or NULL */
+  float* out_attr;            /* [V][H][W][n_attr], or NULL (n_attr == 0) */
+  uint32_t* counts;           /* [V][4] covered, drawn, clipped, outside; or NULL */
+  void* workspace;            /* >= sr_cloud_render_workspace(...) bytes, 16-byte aligned, stream-ordered reuse */
+  int64_t workspace_bytes;
+} sr_cloud_render_desc;
+
+/* Bytes of workspace: the key image (V H W 64-bit words) and the counts.  Never shrinks when an argument
+ * grows; 0 for arguments sr_cloud_render would reject. */
+int64_t sr_cloud_render_workspace(int n_views, int height, int width);
+/* Three launches, asynchronous and allocation-free.  SR_EINVAL for a null desc, points, extrinsic, intrinsic
+ * or workspace; n outside [1, 2^31 - 1]; ldp < 3; n_attr outside [0, 8]; n_attr > 0 with a NULL attr, a NULL
+ * out_attr or lda < n_attr; exactly one of view_id and exclude; n_views outside [1, 65535]; height or width
+ * below 1; n_views * height * width above 2^31 - 1; radius outside [0, 3]; a z_near that is not finite or
+ * <= 0; a z_far that is a NaN or below z_near; no output at all (depth, index, out_attr and counts all
+ * NULL); a workspace that is too small or not 16-byte aligned; an xform that is not 8-byte aligned. */
+int sr_cloud_render(sr_stream_t stream, const sr_cloud_render_desc* desc);
+
 #ifdef __cplusplus
 }
 #endif

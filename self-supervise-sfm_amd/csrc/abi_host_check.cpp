@@ -14,6 +14,7 @@
 //   abi_host_check layout depth_eval   the same for sr_select_desc and sr_depth_eval_desc (ABI 1.12)
 //   abi_host_check layout cloud_voxel   the same for sr_sort_desc and sr_cloud_voxel_desc (ABI 1.13)
 //   abi_host_check layout sparsify   the same for sr_sparsify_desc (ABI 1.14)
+//   abi_host_check layout cloud_render   the same for sr_cloud_render_desc (ABI 1.15)
 //   abi_host_check check    the validation sweep; exit 0 iff every call returned what it should
 #include <cstddef>
 #include <cstdio>
@@ -220,6 +221,22 @@ void layout_sparsify() {
           FIELD(sr_sparsify_desc, row_stride), FIELD(sr_sparsify_desc, n_groups), FIELD(sr_sparsify_desc, n_steps),
           FIELD(sr_sparsify_desc, order), FIELD(sr_sparsify_desc, bin_sum), FIELD(sr_sparsify_desc, cut),
           FIELD(sr_sparsify_desc, count), FIELD(sr_sparsify_desc, workspace), FIELD(sr_sparsify_desc, workspace_bytes)));
+  std::printf("}\n");
+}
+
+void layout_cloud_render() {
+  const char* sep = "";
+  std::printf("{");
+  STRUCT(sr_cloud_render_desc,
+         (FIELD(sr_cloud_render_desc, points), FIELD(sr_cloud_render_desc, attr), FIELD(sr_cloud_render_desc, mask),
+          FIELD(sr_cloud_render_desc, view_id), FIELD(sr_cloud_render_desc, exclude), FIELD(sr_cloud_render_desc, xform),
+          FIELD(sr_cloud_render_desc, extrinsic), FIELD(sr_cloud_render_desc, intrinsic), FIELD(sr_cloud_render_desc, n),
+          FIELD(sr_cloud_render_desc, ldp), FIELD(sr_cloud_render_desc, lda), FIELD(sr_cloud_render_desc, n_attr),
+          FIELD(sr_cloud_render_desc, n_views), FIELD(sr_cloud_render_desc, height), FIELD(sr_cloud_render_desc, width),
+          FIELD(sr_cloud_render_desc, radius), FIELD(sr_cloud_render_desc, z_near), FIELD(sr_cloud_render_desc, z_far),
+          FIELD(sr_cloud_render_desc, attr_fill), FIELD(sr_cloud_render_desc, depth), FIELD(sr_cloud_render_desc, index),
+          FIELD(sr_cloud_render_desc, out_attr), FIELD(sr_cloud_render_desc, counts), FIELD(sr_cloud_render_desc, workspace),
+          FIELD(sr_cloud_render_desc, workspace_bytes)));
   std::printf("}\n");
 }
 
@@ -1158,6 +1175,126 @@ void check() {
     v = sd, v.bin_sum = (double*)((char*)fake(4) + 4);
     expect("sr_sparsify bin_sum % 8", sr_sparsify(nullptr, &v), false);
   }
+  {
+    // ---- sr_cloud_render (ABI 1.15): the workspace sweep, the planned shapes up to the launch, every rejection
+    const int64_t big = 32LL * 518 * 518, most = 2147483647LL;
+    const uint64_t inf_bits = 0x7ff0000000000000ull, nan_bits = 0x7ff8000000000000ull;
+    double inf64, nan64;
+    std::memcpy(&inf64, &inf_bits, 8), std::memcpy(&nan64, &nan_bits, 8);
+    {  // never shrinks when an argument grows; 0 for what the call rejects
+      const int vs[] = {1, 2, 3, 32, 65535}, hs[] = {1, 2, 37, 518, 1024}, ws[] = {1, 2, 53, 518, 2047};
+      for (int v : vs)
+        for (int h : hs)
+          for (int w : ws) {
+            const int64_t pix = (int64_t)v * h * w;
+            const int64_t b = sr_cloud_render_workspace(v, h, w);
+            if (pix > most) {
+              if (b != 0) ++g_fail;
+              continue;
+            }
+            if (b <= 0 || b % 16 || b < 8 * pix + 16 * (int64_t)v) ++g_fail;
+            if (pix + (int64_t)h * w <= most && v < 65535 && sr_cloud_render_workspace(v + 1, h, w) < b) ++g_fail;
+            if (pix + (int64_t)v * w <= most && sr_cloud_render_workspace(v, h + 1, w) < b) ++g_fail;
+            if (pix + (int64_t)v * h <= most && sr_cloud_render_workspace(v, h, w + 1) < b) ++g_fail;
+          }
+      if (sr_cloud_render_workspace(0, 5, 5) || sr_cloud_render_workspace(-1, 5, 5) || sr_cloud_render_workspace(65536, 1, 1) ||
+          sr_cloud_render_workspace(1, 0, 5) || sr_cloud_render_workspace(1, 5, 0) || sr_cloud_render_workspace(1, -3, 5) ||
+          sr_cloud_render_workspace(1, 1 << 16, 1 << 15) || sr_cloud_render_workspace(2, 1 << 15, 1 << 15) ||
+          sr_cloud_render_workspace(65535, 2147483647, 2147483647) || sr_cloud_render_workspace(1, 2147483647, 1) <= 0 ||
+          sr_cloud_render_workspace(1, 1, 2147483647) <= 0 || sr_cloud_render_workspace(65535, 1, 1) <= 0)
+        ++g_fail;
+      std::printf("render workspace bytes at 32 x 518 x 518: %lld\n", (long long)sr_cloud_render_workspace(32, 518, 518));
+    }
+    sr_cloud_render_desc rd{};
+    rd.points = fake<float>(0), rd.attr = fake<float>(1), rd.mask = fake<uint8_t>(2), rd.view_id = fake<int32_t>(3);
+    rd.exclude = fake<int32_t>(4), rd.xform = fake<double>(5), rd.extrinsic = fake<float>(6), rd.intrinsic = fake<float>(7);
+    rd.n = big, rd.ldp = 3, rd.lda = 4, rd.n_attr = 4, rd.n_views = 32, rd.height = 518, rd.width = 518, rd.radius = 1;
+    rd.z_near = 1e-6, rd.z_far = inf64, rd.attr_fill = 0.5f;
+    rd.depth = fake<float>(8), rd.index = fake<int32_t>(9), rd.out_attr = fake<float>(10), rd.counts = fake<uint32_t>(11);
+    rd.workspace = fake(12), rd.workspace_bytes = sr_cloud_render_workspace(32, 518, 518);
+    expect("sr_cloud_render 32 x 518 x 518, every output", sr_cloud_render(nullptr, &rd), true);
+    sr_cloud_render_desc u = rd;
+    u.attr = nullptr, u.out_attr = nullptr, u.n_attr = 0, u.lda = 0, u.mask = nullptr, u.view_id = nullptr, u.exclude = nullptr;
+    u.xform = nullptr, u.index = nullptr, u.counts = nullptr, u.radius = 0;
+    expect("sr_cloud_render bare, depth only", sr_cloud_render(nullptr, &u), true);
+    u = rd, u.depth = nullptr, u.index = nullptr, u.out_attr = nullptr, u.attr = nullptr, u.n_attr = 0;
+    expect("sr_cloud_render counts only", sr_cloud_render(nullptr, &u), true);
+    for (int r = 0; r <= 3; ++r) {
+      u = rd, u.radius = r, u.ldp = 5, u.lda = 9, u.n_attr = 8, u.z_far = u.z_near;
+      expect("sr_cloud_render radius sweep, padded rows", sr_cloud_render(nullptr, &u), true);
+    }
+    u = rd, u.n = 1, u.n_views = 1, u.height = 1, u.width = 1;
+    expect("sr_cloud_render one point, one pixel", sr_cloud_render(nullptr, &u), true);
+    u = rd, u.n = most, u.n_views = 65535, u.height = 1, u.width = 1, u.workspace_bytes = sr_cloud_render_workspace(65535, 1, 1);
+    expect("sr_cloud_render 2^31 - 1 points, 65535 views", sr_cloud_render(nullptr, &u), true);
+    u = rd, u.n_views = 1, u.height = 1, u.width = 2147483647, u.workspace_bytes = sr_cloud_render_workspace(1, 1, 2147483647);
+    expect("sr_cloud_render 2^31 - 1 pixels", sr_cloud_render(nullptr, &u), true);
+    expect("sr_cloud_render null desc", sr_cloud_render(nullptr, nullptr), false);
+    u = rd, u.points = nullptr;
+    expect("sr_cloud_render null points", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.extrinsic = nullptr;
+    expect("sr_cloud_render null extrinsic", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.intrinsic = nullptr;
+    expect("sr_cloud_render null intrinsic", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.workspace = nullptr;
+    expect("sr_cloud_render null workspace", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.n = 0;
+    expect("sr_cloud_render n 0", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.n = most + 1;
+    expect("sr_cloud_render n 2^31", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.ldp = 2;
+    expect("sr_cloud_render ldp 2", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.n_attr = -1;
+    expect("sr_cloud_render n_attr -1", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.n_attr = 9, u.lda = 9;
+    expect("sr_cloud_render n_attr 9", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.attr = nullptr;
+    expect("sr_cloud_render n_attr without attr", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.out_attr = nullptr;
+    expect("sr_cloud_render n_attr without out_attr", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.lda = 3;
+    expect("sr_cloud_render lda < n_attr", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.exclude = nullptr;
+    expect("sr_cloud_render view_id without exclude", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.view_id = nullptr;
+    expect("sr_cloud_render exclude without view_id", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.n_views = 0;
+    expect("sr_cloud_render n_views 0", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.n_views = 65536, u.height = 1, u.width = 1, u.workspace_bytes = int64_t(1) << 50;
+    expect("sr_cloud_render n_views 65536", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.height = 0;
+    expect("sr_cloud_render height 0", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.width = -4;
+    expect("sr_cloud_render width -4", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.n_views = 8004, u.workspace_bytes = int64_t(1) << 50;
+    expect("sr_cloud_render 2^31 pixels and more", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.n_views = 65535, u.height = 2147483647, u.width = 2147483647, u.workspace_bytes = int64_t(1) << 50;
+    expect("sr_cloud_render a product that overflows", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.radius = -1;
+    expect("sr_cloud_render radius -1", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.radius = 4;
+    expect("sr_cloud_render radius 4", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.z_near = 0.0;
+    expect("sr_cloud_render z_near 0", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.z_near = -1.0;
+    expect("sr_cloud_render z_near -1", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.z_near = nan64;
+    expect("sr_cloud_render z_near NaN", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.z_near = inf64;
+    expect("sr_cloud_render z_near Inf", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.z_far = nan64;
+    expect("sr_cloud_render z_far NaN", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.z_near = 2.0, u.z_far = 1.0;
+    expect("sr_cloud_render z_far < z_near", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.depth = nullptr, u.index = nullptr, u.counts = nullptr, u.attr = nullptr, u.out_attr = nullptr, u.n_attr = 0;
+    expect("sr_cloud_render no output", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.workspace_bytes -= 1;
+    expect("sr_cloud_render workspace one byte short", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.workspace = (char*)fake(12) + 8;
+    expect("sr_cloud_render workspace % 16", sr_cloud_render(nullptr, &u), false);
+    u = rd, u.xform = (const double*)((const char*)fake(5) + 4);
+    expect("sr_cloud_render xform % 8", sr_cloud_render(nullptr, &u), false);
+  }
   expect("sr_pose_decode_f32 null", sr_pose_decode_f32(nullptr, nullptr, 9, 0, 518, 518, nullptr, nullptr), false);
   expect("sr_copy_rows_f32 null", sr_copy_rows_f32(nullptr, nullptr, 0, nullptr, 0, nullptr, 0, 0), false);
   expect("sr_conv3x3_f32 null", sr_conv3x3_f32(nullptr, nullptr, 1, 8, 8, 32, 1, 0, nullptr, 32, SR_EPI_BIAS, &ep, nullptr, 32, nullptr), false);
@@ -1239,6 +1376,8 @@ int main(int argc, char** argv) {
       layout_cloud_voxel();
     else if (argc > 2 && std::string(argv[2]) == "sparsify")
       layout_sparsify();
+    else if (argc > 2 && std::string(argv[2]) == "cloud_render")
+      layout_cloud_render();
     else
       layout();
     return 0;

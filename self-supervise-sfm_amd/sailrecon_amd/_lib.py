@@ -230,6 +230,20 @@ class SparsifyDesc(ctypes.Structure):
     ]
 
 
+SR_RENDER_MAX_ATTR, SR_RENDER_MAX_RADIUS = 8, 3
+
+
+class CloudRenderDesc(ctypes.Structure):
+    """sr_cloud_render_desc (include/sfm_amd.h)."""
+    _fields_ = [
+        ("points", _vp), ("attr", _vp), ("mask", _vp), ("view_id", _vp), ("exclude", _vp), ("xform", _vp),
+        ("extrinsic", _vp), ("intrinsic", _vp), ("n", _i64), ("ldp", _i64), ("lda", _i64), ("n_attr", _i32),
+        ("n_views", _i32), ("height", _i32), ("width", _i32), ("radius", _i32), ("z_near", ctypes.c_double),
+        ("z_far", ctypes.c_double), ("attr_fill", _f32), ("depth", _vp), ("index", _vp), ("out_attr", _vp),
+        ("counts", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
+    ]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "sr_last_error": (ctypes.c_char_p, []),
@@ -341,6 +355,8 @@ _PROTOS = {
     "sr_cloud_voxel": (_i32, [_vp, ctypes.POINTER(CloudVoxelDesc)]),
     "sr_sparsify_workspace": (_i64, [_i64, _i64, _i32, _i32]),
     "sr_sparsify": (_i32, [_vp, ctypes.POINTER(SparsifyDesc)]),
+    "sr_cloud_render_workspace": (_i64, [_i32, _i32, _i32]),
+    "sr_cloud_render": (_i32, [_vp, ctypes.POINTER(CloudRenderDesc)]),
 }
 EXPORTED = tuple(_PROTOS)
 

@@ -1716,6 +1716,79 @@ def sparsify(err: Tensor, conf: Tensor, n_steps: int, bin_sum: Tensor, *, mask: 
     check(_lib.load().sr_sparsify(_stream(err), ctypes.byref(d)), "sr_sparsify")
 
 
+# ---------------------------------------------------------------- rendering point clouds (utils/cloud_render.py)
+def cloud_render_workspace_bytes(n_views: int, height: int, width: int) -> int:
+    """sr_cloud_render_workspace (0 for arguments sr_cloud_render rejects)."""
+    n_views, height, width = int(n_views), int(height), int(width)
+    if not all(-2 ** 31 <= v < 2 ** 31 for v in (n_views, height, width)):
+        return 0
+    return int(_lib.load().sr_cloud_render_workspace(n_views, height, width))
+
+
+def cloud_render(points: Tensor, extrinsic: Tensor, intrinsic: Tensor, hw, *, attr: Optional[Tensor] = None,
+                 n_attr: Optional[int] = None, mask: Optional[Tensor] = None, view_id: Optional[Tensor] = None,
+                 exclude: Optional[Tensor] = None, xform: Optional[Tensor] = None, radius: int = 0,
+                 z_near: float = 1e-6, z_far: float = float("inf"), attr_fill: float = float("nan"),
+                 depth: Optional[Tensor] = None, index: Optional[Tensor] = None, out_attr: Optional[Tensor] = None,
+                 counts: Optional[Tensor] = None) -> None:
+    """sr_cloud_render: ``points`` [n, >= 3] fp32 (contiguous rows; the first three columns are read) drawn into
+    the V cameras ``extrinsic`` [V, 3, 4] / ``intrinsic`` [V, 3, 3] fp32 (camera from world, OpenCV) at
+    ``hw`` = (H, W) with a z-buffer: ``depth`` fp32 and ``index`` int32 of at least V H W entries, ``out_attr``
+    fp32 of at least V H W n_attr (the winner's row of ``attr`` [n, >= n_attr]), ``counts`` int32 of at least
+    4 V (covered, drawn, clipped, outside per view; storage of the unsigned values).  Outputs may be longer than
+    needed: what lies beyond is not written.  ``mask`` [n] uint8; ``view_id`` [n] and ``exclude`` [V] int32 (view v
+    does not draw the points whose view_id is exclude[v]); ``xform`` fp64 [>= 13] (scale, R, t); ``radius`` 0 .. 3
+    is the half width of the square footprint."""
+    n, cols, ldp = _rows(points, "points", torch.float32)
+    if cols < 3:
+        raise ValueError(f"points must be [n, >= 3], got {tuple(points.shape)}")
+    dev = points.device
+    if not isinstance(extrinsic, Tensor) or extrinsic.dtype != torch.float32 or extrinsic.dim() != 3 \
+            or tuple(extrinsic.shape[1:]) != (3, 4) or extrinsic.shape[0] == 0 or not extrinsic.is_contiguous() \
+            or extrinsic.device != dev:
+        raise ValueError(f"extrinsic must be a contiguous fp32 [V, 3, 4] tensor on {dev}")
+    V = extrinsic.shape[0]
+    if not isinstance(intrinsic, Tensor) or intrinsic.dtype != torch.float32 or tuple(intrinsic.shape) != (V, 3, 3) \
+            or not intrinsic.is_contiguous() or intrinsic.device != dev:
+        raise ValueError(f"intrinsic must be a contiguous fp32 [{V}, 3, 3] tensor on {dev}")
+    H, W = (int(v) for v in hw)
+    d = _lib.CloudRenderDesc()
+    if attr is not None:
+        if isinstance(attr, Tensor) and attr.dim() == 2 and attr.shape[1] == 1 and attr.stride(1) != 1:
+            attr = attr.as_strided(attr.shape, (attr.stride(0), 1))  # one column: its stride says nothing (numpy's x[:, None])
+        if _rows(attr, "attr", torch.float32)[0] != n or attr.device != dev:
+            raise ValueError(f"attr must have {n} rows on {dev}")
+        d.lda = attr.stride(0)
+        d.n_attr = attr.shape[1] if n_attr is None else int(n_attr)
+        if d.n_attr > attr.shape[1]:
+            raise ValueError(f"n_attr {d.n_attr} exceeds the {attr.shape[1]} columns of attr")
+    elif n_attr:
+        raise ValueError("n_attr without attr")
+    need = cloud_render_workspace_bytes(V, H, W)
+    if need <= 0:
+        raise ValueError(f"{V} views of {H} x {W} pixels are outside the renderer's range")
+    pix = V * H * W
+    for name, t, dt, cnt in (("depth", depth, torch.float32, pix), ("index", index, torch.int32, pix),
+                             ("out_attr", out_attr, torch.float32, pix * d.n_attr), ("counts", counts, torch.int32, 4 * V)):
+        if t is not None and (not isinstance(t, Tensor) or t.dtype != dt or not t.is_contiguous() or t.device != dev
+                              or t.numel() < cnt):
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of at least {cnt} entries on {dev}")
+    _out(mask, "mask", torch.uint8, n, points)
+    _out(view_id, "view_id", torch.int32, n, points)
+    _out(exclude, "exclude", torch.int32, V, points)
+    if xform is not None and (xform.dtype != torch.float64 or xform.dim() != 1 or xform.numel() < 13
+                              or not xform.is_contiguous() or xform.device != dev):
+        raise ValueError("xform must be a contiguous fp64 vector of at least 13 entries on the points' device")
+    ws = torch.empty(need, device=dev, dtype=torch.uint8)  # stream-ordered: the caching allocator's rule
+    d.points, d.attr, d.mask, d.view_id, d.exclude, d.xform = _p(points), _p(attr), _p(mask), _p(view_id), _p(exclude), _p(xform)
+    d.extrinsic, d.intrinsic = _p(extrinsic), _p(intrinsic)
+    d.n, d.ldp, d.n_views, d.height, d.width, d.radius = n, ldp, V, H, W, int(radius)
+    d.z_near, d.z_far, d.attr_fill = float(z_near), float(z_far), float(attr_fill)
+    d.depth, d.index, d.out_attr, d.counts = _p(depth), _p(index), _p(out_attr), _p(counts)
+    d.workspace, d.workspace_bytes = _p(ws), need
+    check(_lib.load().sr_cloud_render(_stream(points), ctypes.byref(d)), "sr_cloud_render")
+
+
 # ---------------------------------------------------------------- training step (SURVEY §8(f) rank 4)
 _TRAIN_WS = {}  # ((device, stream), name) -> fp32 workspace
 

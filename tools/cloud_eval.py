@@ -37,6 +37,12 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
 
 def read_ply_xyz(path: str) -> np.ndarray:
     """[N, 3] fp32: the x, y, z properties of a PLY file's vertex element."""
+    return read_ply_columns(path, ("x", "y", "z"))
+
+
+def read_ply_columns(path: str, want=("x", "y", "z"), optional: bool = False):
+    """[N, len(want)] fp32: the properties ``want`` of a PLY file's vertex element.  With ``optional``, None
+    when the element lacks one of them."""
     with open(path, "rb") as f:
         if f.readline().strip() != b"ply":
             raise ValueError(f"{path}: not a PLY file")
@@ -71,17 +77,19 @@ def read_ply_xyz(path: str) -> np.ndarray:
             raise ValueError(f"{path}: the first element must be vertex")
         _, n, props = elements[0]
         names = [p[0] for p in props]
-        if any(c not in names for c in "xyz"):
-            raise ValueError(f"{path}: the vertex element has no x, y, z properties")
+        if any(c not in names for c in want):
+            if optional:
+                return None
+            raise ValueError(f"{path}: the vertex element has no {', '.join(want)} properties")
         if fmt == "binary_little_endian":
             rec = np.dtype([(name, "<" + t) for name, t in props])
             buf = f.read(n * rec.itemsize)
             if len(buf) != n * rec.itemsize:
                 raise ValueError(f"{path}: {n} vertices declared, the file ends after {len(buf) // rec.itemsize}")
             v = np.frombuffer(buf, dtype=rec, count=n)
-            return np.stack([v["x"], v["y"], v["z"]], axis=1).astype(np.float32)
-        cols = [names.index(c) for c in "xyz"]
-        out = np.empty((n, 3), np.float32)
+            return np.stack([v[c] for c in want], axis=1).astype(np.float32)
+        cols = [names.index(c) for c in want]
+        out = np.empty((n, len(want)), np.float32)
         for i in range(n):
             w = f.readline().split()
             if len(w) != len(props):

@@ -1244,6 +1244,107 @@ def sparsify_once_scene():
     sparsify_once(("scene",))
 
 
+def _render_scene(views=32, size=518):
+    """A synthetic scene on the device: ``views`` cameras side by side in front of a wavy wall, every view's
+    depth map unprojected (sr_unproject_depth_f32) into one raster-ordered cloud with r, g, b, conf attributes."""
+    from sailrecon_amd.utils.geometry import unproject_depth_points
+    g = torch.Generator(device=DEV).manual_seed(0)
+    E = torch.zeros(views, 3, 4, device=DEV)
+    E[:, :, :3] = torch.eye(3, device=DEV)
+    E[:, :2, 3] = torch.rand(views, 2, device=DEV, generator=g) - 0.5
+    K = torch.zeros(views, 3, 3, device=DEV)
+    K[:, 0, 0] = K[:, 1, 1] = 0.9 * size
+    K[:, 0, 2] = K[:, 1, 2] = (size - 1) / 2
+    K[:, 2, 2] = 1
+    yy, xx = torch.meshgrid(torch.arange(size, device=DEV), torch.arange(size, device=DEV), indexing="ij")
+    depth = 3 + 0.3 * torch.sin(xx / 40.0)[None] * torch.cos(yy / 55.0)[None] + 0.05 * torch.rand(views, size, size, device=DEV, generator=g)
+    pts = unproject_depth_points(depth, E, K).reshape(-1, 3)
+    attrs = torch.rand(pts.shape[0], 4, device=DEV, generator=g)
+    return pts, attrs, E, K
+
+
+def _render_statement(p, E, K, H, W, radius):
+    """The torch statement of one rendering: per view an fp64 projection and scatter_reduce_("amin") on int64
+    keys (depth bits << 32 | index).  Returns the key images [V, H W]."""
+    n = p.shape[0]
+    idx = torch.arange(n, device=DEV, dtype=torch.int64)
+    pd = p.double()
+    out = torch.full((E.shape[0], H * W), 2 ** 63 - 1, device=DEV, dtype=torch.int64)
+    for v in range(E.shape[0]):
+        e, k = E[v].double(), K[v].double()
+        c = [((e[r, 0] * pd[:, 0] + e[r, 1] * pd[:, 1]) + e[r, 2] * pd[:, 2]) + e[r, 3] for r in range(3)]
+        ix = torch.floor(k[0, 0] * (c[0] / c[2]) + k[0, 2] + 0.5)
+        iy = torch.floor(k[1, 1] * (c[1] / c[2]) + k[1, 2] + 0.5)
+        ok = (c[2] >= 1e-6) & (ix >= 0) & (ix < W) & (iy >= 0) & (iy < H)
+        key = (c[2].float().view(torch.int32).long() << 32) | idx
+        ixl, iyl = ix.long(), iy.long()
+        for dy in range(-radius, radius + 1):
+            for dx in range(-radius, radius + 1):
+                x, y = ixl + dx, iyl + dy
+                m = ok & (x >= 0) & (x < W) & (y >= 0) & (y < H)
+                out[v].scatter_reduce_(0, (y * W + x)[m], key[m], "amin")
+    return out
+
+
+def render(runs=3):
+    """The point-cloud renderer (sr_cloud_render) against its torch statement, in alternation in one process,
+    ``runs`` timed runs each after one warm-up, HIP events, each side ending in a D2H copy.  A synthetic 32-view
+    scene's own cloud (32 x 518^2 points in raster order, r g b conf attributes) into its 32 cameras at 518^2,
+    radius 0 and 1; then the same cloud after voxel downsampling.  The statement: per view an fp64 projection and
+    scatter_reduce_("amin") on int64 keys, depth and index only.  Atomics per second: drawn points times the
+    footprint over the whole call's time, a lower bound of the draw kernel's own rate (the kernel trace has it)."""
+    from sailrecon_amd.utils.cloud_export import voxel_downsample
+    size, views = 518, 32
+    pts, attrs, E, K = _render_scene(views, size)
+    vox = voxel_downsample(pts, 0.01, attrs=attrs)
+    shapes = {"scene": (pts, attrs), f"voxel 0.01 ({vox['n_voxels']} points)": (vox["points"].contiguous(), vox["attrs"].contiguous())}
+    depth = torch.empty(views, size, size, device=DEV)
+    index = torch.empty(views, size, size, device=DEV, dtype=torch.int32)
+    out_a = torch.empty(views, size, size, 4, device=DEV)
+    counts = torch.empty(views, 4, device=DEV, dtype=torch.int32)
+    for label, (p, a) in shapes.items():
+        n = p.shape[0]
+        for radius in (0, 1):
+            def ours():
+                ops.cloud_render(p, E, K, (size, size), attr=a, radius=radius, depth=depth, index=index, out_attr=out_a,
+                                 counts=counts)
+                return counts.cpu()
+
+            def theirs():
+                return _render_statement(p, E, K, size, size, radius)[:, :1].cpu()
+
+            times = {"sr_cloud_render": [], "projection + scatter amin": []}
+            fns = {"sr_cloud_render": ours, "projection + scatter amin": theirs}
+            for fn in fns.values():
+                fn()
+            torch.cuda.synchronize()
+            for _ in range(runs):
+                for name, fn in fns.items():
+                    times[name].append(timeit(fn, reps=1, warm=0))
+            tag = f"render {label}, n {n}, V {views}, {size}^2, radius {radius}"
+            for name, ms in times.items():
+                print(f"{tag} {name:26s}: " + " ".join(f"{t:9.3f}" for t in ms) + f" ms  best {min(ms):9.3f} ms", flush=True)
+            c = ours().long() & 0xFFFFFFFF
+            keys = _render_statement(p, E, K, size, size, radius)
+            want_idx = torch.where(keys == 2 ** 63 - 1, -1, keys & 0xFFFFFFFF).int().reshape(views, size, size)
+            best, ref = min(times["sr_cloud_render"]), min(times["projection + scatter amin"])
+            atomics = int(c[:, 1].sum()) * (2 * radius + 1) ** 2
+            print(f"{tag}: sr_cloud_render is {ref / best:.2f} x the statement's speed; same index image: "
+                  f"{bool(torch.equal(index, want_idx))}; drawn {int(c[:, 1].sum())}, covered {int(c[:, 0].sum())} of "
+                  f"{views * size * size} pixels; >= {atomics / (best * 1e-3) / 1e9:.1f} G atomics/s over the whole call; "
+                  f"workspace {ops.cloud_render_workspace_bytes(views, size, size) / 2 ** 20:.0f} MiB, the statement's "
+                  f"keys at once would take {8 * views * n / 2 ** 20:.0f} MiB  [{ops.last_kernel()}]", flush=True)
+
+
+def render_once():
+    """One sr_cloud_render of the 32 x 518^2 scene into its 32 cameras per radius, for a kernel trace of its own."""
+    from sailrecon_amd.utils.cloud_render import render_cloud
+    pts, attrs, E, K = _render_scene()
+    for radius in (0, 1):
+        r = render_cloud(pts, E, K, (518, 518), attrs=attrs, radius=radius)
+        print(radius, r["coverage"][0], flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["attn", "gemm", "ln"]
     for w in which:
