@@ -7,7 +7,7 @@
 // Contract (DESIGN.md "Scoring point clouds"; points are packed [n][3] fp32):
 //   transform   p' = fl32(s (R p) + t): every product and sum in fp64, left to right, none contracted,
 //               from the fp32 point and the fp64 [13] = scale, R row-major, t that sr_pose_align leaves in
-//               out[0..12]; rounded to fp32 once.  The same function serves queries and targets.
+//               out[0..12]; rounded to fp32 once.  sr::load_point (sr_eval.h) serves queries and targets.
 //   distance    d(q) = sqrt(min_t d2(q, t)), d2 = dx dx + dy dy + dz dz in fp32 from the direct
 //               differences dx = q.x - t.x, ... (never |q|^2 + |t|^2 - 2 q.t, which cancels for a cloud far
 //               from the origin); sqrt correctly rounded
@@ -23,9 +23,9 @@
 //   histogram   slot k < n_bins counts k <= fl32(d / bin_len) < k + 1, slot n_bins the larger distances,
 //               slot n_bins + 1 the non-finite queries; integer atomics only
 //   stats       n_finite, sum d, sum d^2, max d, n_nonfinite, 0: fp64 from the fp32 d; a lane's queries in
-//               ascending order, a fixed LDS tree per workgroup, one partial per workgroup in the workspace,
-//               then one workgroup sums the partials (each lane a contiguous ascending run, then the same
-//               tree).  No floating-point atomics.
+//               ascending order, sr::block_reduce's fixed LDS tree per workgroup, one partial per workgroup in the
+//               workspace, then one workgroup sums the partials (each lane a contiguous ascending run, then the
+//               same tree).  No floating-point atomics.
 //
 //   cloud_hist_zero_kernel   clears hist
 //   cloud_prep_kernel        targets -> float4 (x, y, z, 0) in the workspace, transformed, non-finite ones
@@ -37,9 +37,8 @@
 //   cloud_finish_kernel      per query tile: merges the slices, writes dist / index, LDS histogram,
 //                            workgroup partial of the stats
 //   cloud_stats_kernel       one workgroup: sums the partials
-#include <string.h>
-
 #include "sr_common.h"
+#include "sr_eval.h"
 
 namespace {
 
@@ -53,22 +52,7 @@ constexpr int MAX_SLICES = 65535;     // grid.y
 constexpr int AUTO_BLOCKS = 1024;     // workgroups the automatic slice count aims for: 4 per CU
 constexpr int AUTO_MIN_CHUNK = 2048;  // fewest targets of an automatic slice
 
-__device__ inline bool bits_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
-__device__ inline float pos_inf() { return __uint_as_float(0x7f800000u); }
-
-using sr::xform_point;  // fl32(s (R p) + t), shared with sr_cloud_voxel (sr_common.h)
-
-// a point of a packed [n][3] array, transformed; true if it is non-finite before or after
-__device__ inline bool load_point(const float* __restrict__ pts, int64_t i, const double* __restrict__ xform, float& x,
-                                  float& y, float& z) {
-  x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
-  bool bad = bits_nonfinite(x) || bits_nonfinite(y) || bits_nonfinite(z);
-  if (xform) {
-    xform_point(xform, x, y, z);
-    bad = bad || bits_nonfinite(x) || bits_nonfinite(y) || bits_nonfinite(z);
-  }
-  return bad;
-}
+using sr::pos_inf;
 
 struct Plan {
   int64_t chunk;    // targets per slice, a multiple of 64
@@ -126,7 +110,7 @@ __global__ __launch_bounds__(CE_T) void cloud_prep_kernel(Args a) {
   const int64_t i = (int64_t)blockIdx.x * CE_T + threadIdx.x;
   if (i >= a.d.n_target) return;
   float x, y, z;
-  if (load_point(a.d.target, i, a.d.target_xform, x, y, z)) x = y = z = pos_inf();
+  if (sr::load_point(a.d.target + 3 * i, a.d.target_xform, x, y, z)) x = y = z = pos_inf();
   a.tgt4[i] = make_float4(x, y, z, 0.0f);
 }
 
@@ -143,7 +127,7 @@ __global__ __launch_bounds__(CE_T) void cloud_sweep_kernel(Args a) {
     const int64_t q = q0 + k * CE_T + t;
     qx[k] = qy[k] = qz[k] = 0.0f;
     bad[k] = true;
-    if (q < nq) bad[k] = load_point(a.d.query, q, a.d.query_xform, qx[k], qy[k], qz[k]);
+    if (q < nq) bad[k] = sr::load_point(a.d.query + 3 * q, a.d.query_xform, qx[k], qy[k], qz[k]);
     if (bad[k]) qx[k] = qy[k] = qz[k] = 0.0f;  // the sweep runs on finite numbers; the result is discarded
     best[k] = pos_inf();
     bi[k] = -1;
@@ -184,40 +168,10 @@ __global__ __launch_bounds__(CE_T) void cloud_sweep_kernel(Args a) {
     const int64_t q = q0 + k * CE_T + t;
     if (q < nq) {
       uint2 o = make_uint2(__float_as_uint(best[k]), (uint32_t)bi[k]);
-      if (bad[k]) o = make_uint2(0x7f800000u, 0xffffffffu);
+      if (bad[k]) o = make_uint2(sr::PINF_BITS, 0xffffffffu);
       a.part[(int64_t)blockIdx.y * nq + q] = o;
     }
   }
-}
-
-// slot of a finite, non-negative distance: always in [0, n_bins]
-__device__ inline int dist_slot(float d, float bin_len, int n_bins) {
-  const float q = __fdiv_rn(d, bin_len);
-  if (!(q < (float)n_bins)) return n_bins;
-  return min(max((int)q, 0), n_bins);
-}
-
-// sums of NV values and one maximum over the workgroup, in a fixed tree; the results in thread 0
-template <int NV>
-__device__ inline void block_reduce(double (&v)[NV], double& mx, double* smem) {
-  const int t = threadIdx.x;
-  __syncthreads();
-#pragma unroll
-  for (int e = 0; e < NV; ++e) smem[e * CE_T + t] = v[e];
-  smem[NV * CE_T + t] = mx;
-  __syncthreads();
-  for (int s = CE_T / 2; s > 0; s >>= 1) {
-    if (t < s) {
-#pragma unroll
-      for (int e = 0; e < NV; ++e) smem[e * CE_T + t] += smem[e * CE_T + t + s];
-      const double o = smem[NV * CE_T + t + s];
-      if (o > smem[NV * CE_T + t]) smem[NV * CE_T + t] = o;
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int e = 0; e < NV; ++e) v[e] = smem[e * CE_T];
-  mx = smem[NV * CE_T];
 }
 
 __global__ __launch_bounds__(CE_T) void cloud_finish_kernel(Args a) {
@@ -226,11 +180,10 @@ __global__ __launch_bounds__(CE_T) void cloud_finish_kernel(Args a) {
   const int t = threadIdx.x, n_slots = a.d.n_bins + 2;
   const int64_t nq = a.d.n_query, q0 = (int64_t)blockIdx.x * QTILE;
   if (a.d.hist) {
-    for (int e = t; e < n_slots; e += CE_T) s_hist[e] = 0;
+    sr::hist_clear<CE_T>(s_hist, n_slots);
     __syncthreads();
   }
-  double acc[4] = {0.0, 0.0, 0.0, 0.0};  // n_finite, sum d, sum d^2, n_nonfinite
-  double mx = 0.0;
+  double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};  // n_finite, sum d, sum d^2, n_nonfinite, max d
 #pragma unroll 1
   for (int k = 0; k < QPL; ++k) {
     const int64_t q = q0 + k * CE_T + t;
@@ -248,9 +201,9 @@ __global__ __launch_bounds__(CE_T) void cloud_finish_kernel(Args a) {
     const bool bad = bi < 0;
     const float d = __fsqrt_rn(bad ? 0.0f : best);
     // the NaN leaves as bits: under -fno-honor-nans a float select may drop it
-    if (a.d.dist) reinterpret_cast<uint32_t*>(a.d.dist)[q] = bad ? 0x7fc00000u : __float_as_uint(d);
+    if (a.d.dist) reinterpret_cast<uint32_t*>(a.d.dist)[q] = bad ? sr::QNAN_BITS : __float_as_uint(d);
     if (a.d.index) a.d.index[q] = bi;
-    if (a.d.hist) atomicAdd(&s_hist[bad ? a.d.n_bins + 1 : dist_slot(d, a.d.bin_len, a.d.n_bins)], 1u);
+    if (a.d.hist) atomicAdd(&s_hist[bad ? a.d.n_bins + 1 : sr::hist_slot(d, a.d.bin_len, a.d.n_bins)], 1u);
     if (bad) {
       acc[3] += 1.0;
     } else {
@@ -258,21 +211,18 @@ __global__ __launch_bounds__(CE_T) void cloud_finish_kernel(Args a) {
       acc[0] += 1.0;
       acc[1] += dd;
       acc[2] += dd * dd;
-      if (dd > mx) mx = dd;
+      if (dd > acc[4]) acc[4] = dd;
     }
   }
   if (a.d.hist) {
     __syncthreads();
-    for (int e = t; e < n_slots; e += CE_T) {
-      const uint32_t v = s_hist[e];
-      if (v) atomicAdd(&a.d.hist[e], v);
-    }
+    sr::hist_flush<CE_T>(s_hist, a.d.hist, n_slots);
   }
   if (a.d.stats) {
-    block_reduce(acc, mx, s_red);
+    sr::block_reduce<CE_T, 5, true>(acc, s_red);
     if (t == 0) {
       double* o = a.stat + 5 * (int64_t)blockIdx.x;
-      o[0] = acc[0], o[1] = acc[1], o[2] = acc[2], o[3] = mx, o[4] = acc[3];
+      o[0] = acc[0], o[1] = acc[1], o[2] = acc[2], o[3] = acc[4], o[4] = acc[3];
     }
   }
 }
@@ -282,28 +232,20 @@ __global__ __launch_bounds__(CE_T) void cloud_stats_kernel(Args a) {
   const int t = threadIdx.x;
   const int64_t run = (a.n_tiles + CE_T - 1) / CE_T;
   const int64_t lo = run * t, hi = lo + run < a.n_tiles ? lo + run : a.n_tiles;
-  double acc[4] = {0.0, 0.0, 0.0, 0.0};
-  double mx = 0.0;
+  double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};  // as in cloud_finish_kernel
   for (int64_t b = lo; b < hi; ++b) {  // ascending workgroups
     const double* p = a.stat + 5 * b;
     acc[0] += p[0];
     acc[1] += p[1];
     acc[2] += p[2];
     acc[3] += p[4];
-    if (p[3] > mx) mx = p[3];
+    if (p[3] > acc[4]) acc[4] = p[3];
   }
-  block_reduce(acc, mx, s_red);
+  sr::block_reduce<CE_T, 5, true>(acc, s_red);
   if (t == 0) {
     double* o = a.d.stats;
-    o[0] = acc[0], o[1] = acc[1], o[2] = acc[2], o[3] = mx, o[4] = acc[3], o[5] = 0.0;
+    o[0] = acc[0], o[1] = acc[1], o[2] = acc[2], o[3] = acc[4], o[4] = acc[3], o[5] = 0.0;
   }
-}
-
-// positive and finite, on the bits (host code is built with -fno-honor-nans too)
-bool positive_finite(float x) {
-  uint32_t u;
-  memcpy(&u, &x, sizeof(u));
-  return u > 0u && u < 0x7f800000u;
 }
 
 }  // namespace
@@ -325,7 +267,7 @@ extern "C" int sr_cloud_nn(sr_stream_t stream, const sr_cloud_nn_desc* desc) {
   SR_CHECK(d.dist || d.index || d.hist || d.stats, SR_EINVAL, "sr_cloud_nn: every output is NULL");
   if (d.hist) {
     SR_CHECK(d.n_bins > 0 && d.n_bins <= MAX_BINS, SR_EINVAL, "sr_cloud_nn: n_bins %d outside [1, %d]", d.n_bins, MAX_BINS);
-    SR_CHECK(positive_finite(d.bin_len), SR_EINVAL, "sr_cloud_nn: bin_len must be positive and finite");
+    SR_CHECK(sr::positive_finite(d.bin_len), SR_EINVAL, "sr_cloud_nn: bin_len must be positive and finite");
   }
   SR_CHECK(d.target_chunk >= 0 && d.target_chunk % 64 == 0, SR_EINVAL,
            "sr_cloud_nn: target_chunk %d must be 0 or a positive multiple of 64", d.target_chunk);
@@ -333,9 +275,7 @@ extern "C" int sr_cloud_nn(sr_stream_t stream, const sr_cloud_nn_desc* desc) {
   SR_CHECK(make_plan(d.n_query, d.n_target, d.target_chunk, p), SR_EINVAL,
            "sr_cloud_nn: target_chunk %d cuts %lld targets into more than %d slices", d.target_chunk, (long long)d.n_target,
            MAX_SLICES);
-  SR_CHECK(d.workspace_bytes >= p.bytes, SR_EINVAL, "sr_cloud_nn: workspace of %lld bytes, %lld needed",
-           (long long)d.workspace_bytes, (long long)p.bytes);
-  SR_CHECK(((uintptr_t)d.workspace & 15) == 0, SR_EINVAL, "sr_cloud_nn: the workspace must be 16-byte aligned");
+  SR_CHECK_WORKSPACE("sr_cloud_nn", d.workspace, d.workspace_bytes, p.bytes);
   SR_CHECK(((uintptr_t)d.query_xform & 7) == 0 && ((uintptr_t)d.target_xform & 7) == 0 && ((uintptr_t)d.stats & 7) == 0,
            SR_EINVAL, "sr_cloud_nn: fp64 buffers must be 8-byte aligned");
   char* ws = (char*)d.workspace;

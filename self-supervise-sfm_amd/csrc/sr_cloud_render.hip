@@ -5,7 +5,7 @@
 // test on the bits, an integer, or an IEEE fp64 operation that is not contracted.
 //   skipped     (for view v) mask byte 0; a non-finite coordinate; a non-finite transformed point; view_id and
 //               exclude both given and view_id[i] == exclude[v]
-//   q           p, or fl32(s (R p) + t) by sr::xform_point (sr_cloud_nn's transform)
+//   q           p, or fl32(s (R p) + t) by sr::xform_point (sr_eval.h; sr_cloud_nn's transform)
 //   camera      E = extrinsic[v], fp32 [3][4], camera from world, OpenCV, widened exactly;
 //               c_r = ((E[r][0] q_x + E[r][1] q_y) + E[r][2] q_z) + E[r][3] in fp64
 //   clipped     a non-finite c_r (on the bits), c_z < z_near or c_z > z_far, compared in fp64
@@ -45,9 +45,8 @@
 //
 // The Makefile builds this file with -ffp-contract=off -fhonor-nans, for sr_cloud_voxel.hip's two reasons: the
 // shared transform's products and sums are header code, and the tests on the exponent bits must see NaNs.
-#include <string.h>
-
 #include "sr_common.h"
+#include "sr_eval.h"
 
 #ifndef SR_RENDER_PRETEST
 #define SR_RENDER_PRETEST 1
@@ -61,12 +60,10 @@ constexpr int RD_SLOTS = 64;   // partial counts per view: a workgroup adds to s
                                // (point tiles x views) workgroups do not queue on three words per view
 constexpr int64_t RD_MAX_N = 2147483647LL;
 constexpr int RD_MAX_VIEWS = 65535;
-constexpr uint32_t RD_QNAN = 0x7fc00000u;
 
-__device__ inline bool bits_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
-__device__ inline bool bits_nonfinite64(double x) {
-  return ((uint64_t)__double_as_longlong(x) & 0x7ff0000000000000ull) == 0x7ff0000000000000ull;
-}
+using sr::bits_nonfinite;
+using sr::bits_nonfinite64;
+using sr::finite64;
 
 struct RenderPlan {
   int64_t pixels;    // V H W
@@ -79,7 +76,7 @@ bool render_plan(int n_views, int height, int width, RenderPlan& p) {
   const int64_t hw = (int64_t)height * width;  // < 2^62
   if (hw > RD_MAX_N || hw * n_views > RD_MAX_N) return false;
   p.pixels = hw * n_views;
-  p.key_bytes = (8 * p.pixels + 15) & ~int64_t(15);
+  p.key_bytes = sr::align16(8 * p.pixels);
   p.off_cnt = p.key_bytes;
   p.off_slots = p.off_cnt + 16 * (int64_t)n_views;
   p.bytes = p.off_slots + 16 * (int64_t)RD_SLOTS * n_views;
@@ -183,7 +180,7 @@ __global__ __launch_bounds__(RD_T) void render_resolve_kernel(RenderArgs a) {
     const uint64_t key = a.keys[px];
     covered = key != ~uint64_t(0);
     const uint32_t i = (uint32_t)key;
-    if (d.depth) reinterpret_cast<uint32_t*>(d.depth)[px] = covered ? (uint32_t)(key >> 32) : RD_QNAN;
+    if (d.depth) reinterpret_cast<uint32_t*>(d.depth)[px] = covered ? (uint32_t)(key >> 32) : sr::QNAN_BITS;
     if (d.index) d.index[px] = covered ? (int32_t)i : -1;
     if (d.out_attr) {
       uint32_t* o = reinterpret_cast<uint32_t*>(d.out_attr) + px * d.n_attr;  // as bits: a float select may not keep them
@@ -204,12 +201,6 @@ __global__ __launch_bounds__(RD_T) void render_resolve_kernel(RenderArgs a) {
     for (int s = 0; s < RD_SLOTS; ++s) sum += a.slots[4 * ((int64_t)v * RD_SLOTS + s) + t];
     a.cnt[4 * v + t] = sum;  // words 1 .. 3; the covered count in word 0 is the other workgroups' atomics
   }
-}
-
-bool finite64(double x) {
-  uint64_t u;
-  memcpy(&u, &x, sizeof(u));
-  return (u & 0x7fffffffffffffffull) < 0x7ff0000000000000ull;
 }
 
 }  // namespace
@@ -245,9 +236,7 @@ extern "C" int sr_cloud_render(sr_stream_t stream, const sr_cloud_render_desc* d
   SR_CHECK(d.z_far >= d.z_near, SR_EINVAL, "sr_cloud_render: z_far must be no NaN and at least z_near");
   SR_CHECK(d.depth || d.index || (d.out_attr && d.n_attr > 0) || d.counts, SR_EINVAL,
            "sr_cloud_render: no output (depth, index, out_attr and counts are all null)");
-  SR_CHECK(d.workspace_bytes >= p.bytes, SR_EINVAL, "sr_cloud_render: workspace of %lld bytes, %lld needed",
-           (long long)d.workspace_bytes, (long long)p.bytes);
-  SR_CHECK(((uintptr_t)d.workspace & 15) == 0, SR_EINVAL, "sr_cloud_render: the workspace must be 16-byte aligned");
+  SR_CHECK_WORKSPACE("sr_cloud_render", d.workspace, d.workspace_bytes, p.bytes);
   SR_CHECK(((uintptr_t)d.xform & 7) == 0, SR_EINVAL, "sr_cloud_render: xform must be 8-byte aligned");
   if (d.n_attr == 0) a.d.out_attr = nullptr, a.d.attr = nullptr;
   char* ws = (char*)d.workspace;

@@ -4,7 +4,7 @@
 // Contract (DESIGN.md "Downsampling point clouds", include/sfm_amd.h).  Everything that decides a result
 // is a test on the bits, an integer, or an IEEE fp64 operation that is not contracted.
 //   skipped     mask byte 0; a non-finite coordinate; under BEST a NaN weight; a non-finite transformed point
-//   q           p, or fl32(s (R p) + t) by sr::xform_point (sr_cloud_nn's transform)
+//   q           p, or fl32(s (R p) + t) by sr::load_point / sr::xform_point (sr_eval.h; sr_cloud_nn's transform)
 //   cell        f = floor(((double)q - origin) / voxel) per axis; considered when -2^(b-1) <= f < 2^(b-1) on
 //               all three, compared in fp64; outside otherwise
 //   key         (u_z << 2b) | (u_y << b) | u_x, u = f + 2^(b-1); 2^(3b) for what is not considered
@@ -15,8 +15,8 @@
 //   sr::sort_launch      sr_sort_pairs' passes on 3b + 1 bits: sorted keys and the permutation
 //   voxel_head_count_kernel   heads (a sorted key that differs from its predecessor and is no sentinel)
 //                        per tile of 2048 sorted positions
-//   voxel_head_scan_kernel    one workgroup: exclusive scan of the tile counts; the total is the voxel count
-//   voxel_head_local_kernel   the row of every sorted position: tile base + a scan inside the workgroup.
+//   voxel_head_scan_kernel    one workgroup: exclusive scan of the tile counts (sr::scan_row); the total is the voxel count
+//   voxel_head_local_kernel   the row of every sorted position: tile base + sr::block_exclusive inside the workgroup.
 //                        Writes the start of every voxel and voxel_of.
 //   voxel_reduce_kernel  one lane per voxel walks its members from its start while the key stays: the
 //                        left-to-right fp64 sum the contract asks for.  A cloud with everything in one
@@ -26,9 +26,8 @@
 // products and sums, which live in headers, are fused into FMAs whatever a pragma here says; without the
 // second the compiler reads the test on the exponent bits as a float classification, assumes that no
 // float is a NaN and reduces it to |x| == Inf, so that a NaN coordinate would count as finite.
-#include <string.h>
-
 #include "sr_common.h"
+#include "sr_eval.h"
 
 namespace {
 
@@ -38,10 +37,8 @@ constexpr int VX_TILE = VX_T * VX_PER;     // 2048
 constexpr int64_t VX_MAX_N = 2147483647LL;
 constexpr int VX_MAX_BITS = 21;
 
-inline int64_t align16(int64_t b) { return (b + 15) & ~int64_t(15); }
-
-__device__ inline bool bits_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
-__device__ inline bool bits_nan(float x) { return (__float_as_uint(x) & 0x7fffffffu) > 0x7f800000u; }
+using sr::align16;
+using sr::finite64;
 
 struct VoxPlan {
   int64_t tiles;
@@ -78,14 +75,7 @@ struct VoxArgs {
 
 // the transformed point of element i; true if it is to be skipped for its coordinates
 __device__ inline bool load_q(const VoxArgs& a, int64_t i, float& x, float& y, float& z) {
-  const float* p = a.d.points + i * a.d.ldp;
-  x = p[0], y = p[1], z = p[2];
-  bool bad = bits_nonfinite(x) || bits_nonfinite(y) || bits_nonfinite(z);
-  if (a.d.xform) {
-    sr::xform_point(a.d.xform, x, y, z);
-    bad = bad || bits_nonfinite(x) || bits_nonfinite(y) || bits_nonfinite(z);
-  }
-  return bad;
+  return sr::load_point(a.d.points + i * a.d.ldp, a.d.xform, x, y, z);
 }
 
 __device__ inline double cell_of(float q, double origin, double voxel) {
@@ -104,7 +94,7 @@ __global__ __launch_bounds__(VX_T) void voxel_key_kernel(VoxArgs a) {
     float x, y, z;
     skipped = load_q(a, i, x, y, z);
     if (d.mask && d.mask[i] == 0) skipped = true;
-    if (d.mode == SR_VOXEL_BEST && d.weight && bits_nan(d.weight[i])) skipped = true;
+    if (d.mode == SR_VOXEL_BEST && d.weight && sr::bits_nan(d.weight[i])) skipped = true;
     uint64_t key = a.sentinel;
     if (!skipped) {
       const double fx = cell_of(x, d.origin[0], d.voxel), fy = cell_of(y, d.origin[1], d.voxel),
@@ -145,51 +135,21 @@ __device__ inline uint32_t head_bits(const VoxArgs& a, int64_t j0, uint64_t (&k)
   return bits;
 }
 
-// exclusive scan of one value per thread over the workgroup; the total in every thread's `total`
-__device__ inline uint32_t block_exclusive(uint32_t v, uint32_t* smem, uint32_t& total) {
-  const int t = threadIdx.x;
-  __syncthreads();
-  smem[t] = v;
-  __syncthreads();
-  for (int off = 1; off < VX_T; off <<= 1) {
-    const uint32_t o = t >= off ? smem[t - off] : 0u;
-    __syncthreads();
-    smem[t] += o;
-    __syncthreads();
-  }
-  total = smem[VX_T - 1];
-  return smem[t] - v;
-}
-
 __global__ __launch_bounds__(VX_T) void voxel_head_count_kernel(VoxArgs a) {
   __shared__ uint32_t s_scan[VX_T];
   const int t = threadIdx.x;
   uint64_t k[VX_PER];
   const uint32_t bits = head_bits(a, (int64_t)blockIdx.x * VX_TILE + (int64_t)t * VX_PER, k);
   uint32_t total;
-  block_exclusive((uint32_t)__popc(bits), s_scan, total);
+  sr::block_exclusive<VX_T>((uint32_t)__popc(bits), s_scan, total);
   if (t == 0) a.tilecnt[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(VX_T) void voxel_head_scan_kernel(VoxArgs a) {
   __shared__ uint32_t s_scan[VX_T];
-  const int t = threadIdx.x;
-  uint32_t carry = 0;
-  for (int64_t c0 = 0; c0 < a.tiles; c0 += 4 * VX_T) {
-    const int64_t e0 = c0 + 4 * t;
-    uint32_t v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = e0 + u < a.tiles ? a.tilecnt[e0 + u] : 0u;
-    uint32_t total;
-    uint32_t run = carry + block_exclusive(v[0] + v[1] + v[2] + v[3], s_scan, total);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      if (e0 + u < a.tiles) a.tilecnt[e0 + u] = run;
-      run += v[u];
-    }
-    carry += total;
-  }
-  if (t == 0) a.cnt[0] = carry;
+  const uint32_t heads = sr::scan_row<VX_T>(a.tiles, 0u, s_scan, [&](int64_t e) { return a.tilecnt[e]; },
+                                            [&](int64_t e, uint32_t x) { a.tilecnt[e] = x; });
+  if (threadIdx.x == 0) a.cnt[0] = heads;
 }
 
 __global__ __launch_bounds__(VX_T) void voxel_head_local_kernel(VoxArgs a) {
@@ -199,7 +159,7 @@ __global__ __launch_bounds__(VX_T) void voxel_head_local_kernel(VoxArgs a) {
   uint64_t k[VX_PER];
   const uint32_t bits = head_bits(a, j0, k);
   uint32_t total;
-  uint32_t row = a.tilecnt[blockIdx.x] + block_exclusive((uint32_t)__popc(bits), s_scan, total);  // heads before j0
+  uint32_t row = a.tilecnt[blockIdx.x] + sr::block_exclusive<VX_T>((uint32_t)__popc(bits), s_scan, total);  // heads before j0
 #pragma unroll
   for (int u = 0; u < VX_PER; ++u) {
     const int64_t j = j0 + u;
@@ -274,13 +234,6 @@ __global__ __launch_bounds__(VX_T) void voxel_reduce_kernel(VoxArgs a) {
   if (d.out_key) d.out_key[v] = key;
 }
 
-// finite, on the bits
-bool finite64(double x) {
-  uint64_t u;
-  memcpy(&u, &x, sizeof(u));
-  return (u & 0x7fffffffffffffffull) < 0x7ff0000000000000ull;
-}
-
 }  // namespace
 
 extern "C" int64_t sr_cloud_voxel_workspace(int64_t n) {
@@ -311,9 +264,7 @@ extern "C" int sr_cloud_voxel(sr_stream_t stream, const sr_cloud_voxel_desc* des
            (long long)d.capacity, (long long)d.n);
   VoxPlan p;
   vox_plan(d.n, p);
-  SR_CHECK(d.workspace_bytes >= p.bytes, SR_EINVAL, "sr_cloud_voxel: workspace of %lld bytes, %lld needed",
-           (long long)d.workspace_bytes, (long long)p.bytes);
-  SR_CHECK(((uintptr_t)d.workspace & 15) == 0, SR_EINVAL, "sr_cloud_voxel: the workspace must be 16-byte aligned");
+  SR_CHECK_WORKSPACE("sr_cloud_voxel", d.workspace, d.workspace_bytes, p.bytes);
   SR_CHECK(((uintptr_t)d.xform & 7) == 0 && ((uintptr_t)d.out_key & 7) == 0, SR_EINVAL,
            "sr_cloud_voxel: xform and out_key must be 8-byte aligned");
   char* ws = (char*)d.workspace;

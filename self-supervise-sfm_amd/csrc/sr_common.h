@@ -136,21 +136,6 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
-// fl32(s (R p) + t) from the fp32 point and the fp64 [13] = scale, R row-major, t: fp64, left to right, rounded
-// to fp32 once.  The one transform of sr_cloud_nn and sr_cloud_voxel.  __dmul_rn / __dadd_rn are plain * and +
-// in the HIP headers, so whether they stay unfused is the including object's -ffp-contract: sr_cloud_voxel.o
-// is built with it off (bit for bit what numpy computes), sr_cloud_eval.o as it always was.
-__device__ inline void xform_point(const double* __restrict__ x, float& px, float& py, float& pz) {
-  const double a = (double)px, b = (double)py, c = (double)pz;
-  float o[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    const double rp = __dadd_rn(__dadd_rn(__dmul_rn(x[1 + 3 * r], a), __dmul_rn(x[2 + 3 * r], b)), __dmul_rn(x[3 + 3 * r], c));
-    o[r] = (float)__dadd_rn(__dmul_rn(x[0], rp), x[10 + r]);
-  }
-  px = o[0], py = o[1], pz = o[2];
-}
-
 __device__ __forceinline__ void wait_vmcnt0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 // raw workgroup barrier that does NOT drain in-flight LDS-DMA (vmcnt); memory clobbers keep

@@ -13,7 +13,7 @@
 //                        otherwise serialise 64 lanes on one LDS word.  An element counts for rank r
 //                        when its higher digits equal r's prefix.  Non-zero bins are flushed with
 //                        integer atomics.  In the first pass the ranks share histogram 0.
-//   select_scan_kernel   one workgroup per group: an LDS scan of the 256 bins of every rank finds the
+//   select_scan_kernel   one workgroup per group: sr::block_exclusive over the 256 bins of every rank finds the
 //                        bin holding the remaining rank, appends it to the prefix, subtracts the bins
 //                        below, clears the counters for the next pass; the last pass writes the values.
 //   Rows are re-read from global memory in every pass (4 x 4 bytes per element): staging a row once
@@ -28,9 +28,8 @@
 //   depth_error_kernel     a, the error terms, LDS histogram, 13 partials per workgroup
 //   depth_group_kernel     one workgroup per group: sums the 13 partials of its views
 //   depth_pool_kernel      row n_groups of stats and hist from the group rows, ascending
-#include <string.h>
-
 #include "sr_common.h"
+#include "sr_eval.h"
 
 #pragma clang fp contract(off)
 
@@ -47,15 +46,12 @@ constexpr int MAX_VIEWS = 65535;
 constexpr int PPL = 8;                         // pixels per lane of the depth kernels
 constexpr int DTILE = DE_T * PPL;              // pixels per workgroup
 constexpr int NE = 13;                         // partials of the error kernel: 12 sums and the maximum
-constexpr uint32_t QNAN_BITS = 0x7fc00000u;
 
-__device__ inline uint32_t sel_key(uint32_t b) { return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u); }
-__device__ inline uint32_t sel_bits(uint32_t k) { return (k >> 31) ? (k ^ 0x80000000u) : ~k; }
-__device__ inline bool bits_finite(uint32_t b) { return (b & 0x7f800000u) != 0x7f800000u; }
-__device__ inline bool bits_nan(uint32_t b) { return (b & 0x7fffffffu) > 0x7f800000u; }
-__device__ inline bool bits_positive_finite(uint32_t b) { return b > 0u && b < 0x7f800000u; }
-
-inline int64_t align16(int64_t b) { return (b + 15) & ~int64_t(15); }
+using sr::align16;
+using sr::bits_finite;
+using sr::bits_nan;
+using sr::bits_positive_finite;
+using sr::QNAN_BITS;
 
 // ------------------------------------------------------------------------------------------ select
 struct SelArgs {
@@ -152,7 +148,7 @@ __global__ __launch_bounds__(DE_T) void select_hist_kernel(SelArgs a, int pass) 
         ++skipped;
         continue;
       }
-      const uint32_t key = sel_key(b[u]);
+      const uint32_t key = sr::key32(b[u]);
       const int digit = (int)((key >> shift) & 255u);
 #pragma unroll
       for (int r = 0; r < SR_SELECT_MAX_RANKS; ++r) {
@@ -186,15 +182,8 @@ __global__ __launch_bounds__(DE_T) void select_scan_kernel(SelArgs a, int pass) 
   uint32_t* hist = a.hist + g * a.n_ranks * 256;
   for (int r = 0; r < a.n_ranks; ++r) {
     const uint32_t c = hist[(pass == 0 ? 0 : r) * 256 + t];
-    s_scan[t] = c;
-    __syncthreads();
-    for (int off = 1; off < DE_T; off <<= 1) {
-      const uint32_t v = t >= off ? s_scan[t - off] : 0u;
-      __syncthreads();
-      s_scan[t] += v;
-      __syncthreads();
-    }
-    const uint32_t incl = s_scan[t], excl = incl - c, n = s_scan[DE_T - 1];
+    uint32_t n;
+    const uint32_t excl = sr::block_exclusive<DE_T>(c, s_scan, n), incl = excl + c;
     uint32_t* st = a.state + (g * a.n_ranks + r) * 2;
     uint32_t rem;
     if (pass == 0) {
@@ -215,7 +204,7 @@ __global__ __launch_bounds__(DE_T) void select_scan_kernel(SelArgs a, int pass) 
   if (pass == 3) {
     const uint32_t n = a.cnt[2 * g];
     if (t < a.n_ranks)
-      reinterpret_cast<uint32_t*>(a.value)[g * a.n_ranks + t] = n ? sel_bits(a.state[(g * a.n_ranks + t) * 2]) : QNAN_BITS;
+      reinterpret_cast<uint32_t*>(a.value)[g * a.n_ranks + t] = n ? sr::unkey32(a.state[(g * a.n_ranks + t) * 2]) : QNAN_BITS;
     if (a.count && t < 2) a.count[2 * g + t] = a.cnt[2 * g + t];
   }
 }
@@ -248,34 +237,8 @@ struct DepArgs {
   int wpv;         // workgroups per view
 };
 
-// sums of NV values over the workgroup in a fixed tree, the last one a maximum if LAST_MAX; results in thread 0
-template <int NV, bool LAST_MAX>
-__device__ inline void block_reduce(double (&v)[NV], double* smem) {
-  const int t = threadIdx.x;
-  __syncthreads();
-#pragma unroll
-  for (int e = 0; e < NV; ++e) smem[e * DE_T + t] = v[e];
-  __syncthreads();
-  for (int s = DE_T / 2; s > 0; s >>= 1) {
-    if (t < s) {
-#pragma unroll
-      for (int e = 0; e < NV; ++e) {
-        const double o = smem[e * DE_T + t + s];
-        if (LAST_MAX && e == NV - 1) {
-          if (o > smem[e * DE_T + t]) smem[e * DE_T + t] = o;
-        } else {
-          smem[e * DE_T + t] += o;
-        }
-      }
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int e = 0; e < NV; ++e) v[e] = smem[e * DE_T];
-}
-
 // the partials [view][workgroup][NV] of group g's views: views ascending, a lane's workgroups ascending,
-// then the tree; results in thread 0
+// then sr::block_reduce's tree
 template <int NV, bool LAST_MAX>
 __device__ inline void group_reduce(const DepArgs& a, const double* part, int g, double (&acc)[NV], double* smem) {
   const int t = threadIdx.x;
@@ -296,7 +259,7 @@ __device__ inline void group_reduce(const DepArgs& a, const double* part, int g,
       }
     }
   }
-  block_reduce<NV, LAST_MAX>(acc, smem);
+  sr::block_reduce<DE_T, NV, LAST_MAX>(acc, smem);
 }
 
 __global__ __launch_bounds__(DE_T) void depth_valid_kernel(DepArgs a) {
@@ -328,7 +291,7 @@ __global__ __launch_bounds__(DE_T) void depth_valid_kernel(DepArgs a) {
       acc[4] += __dmul_rn(pd, pd);
     }
   }
-  block_reduce<5, false>(acc, s_red);
+  sr::block_reduce<DE_T>(acc, s_red);
   if (t == 0) {
     double* o = a.part1 + (int64_t)blockIdx.x * 5;
 #pragma unroll
@@ -356,7 +319,7 @@ __global__ __launch_bounds__(DE_T) void depth_centred_kernel(DepArgs a) {
       acc[1] += __dmul_rn(dp, dp);
     }
   }
-  block_reduce<2, false>(acc, s_red);
+  sr::block_reduce<DE_T>(acc, s_red);
   if (t == 0) {
     double* o = a.part2 + (int64_t)blockIdx.x * 2;
     o[0] = acc[0], o[1] = acc[1];
@@ -416,13 +379,6 @@ __global__ __launch_bounds__(DE_T) void depth_fit_kernel(DepArgs a, int stage) {
   if (d.align != SR_DEPTH_ALIGN_GIVEN) d.xform[2 * g] = s, d.xform[2 * g + 1] = sh;
 }
 
-// slot of a finite, non-negative value: always in [0, n_bins]
-__device__ inline int rel_slot(float r, float bin_len, int n_bins) {
-  const float q = __fdiv_rn(r, bin_len);
-  if (!(q < (float)n_bins)) return n_bins;
-  return min(max((int)q, 0), n_bins);
-}
-
 __global__ __launch_bounds__(DE_T) void depth_error_kernel(DepArgs a) {
   __shared__ uint32_t s_hist[MAX_BINS + 2];
   __shared__ double s_red[NE * DE_T];
@@ -435,7 +391,7 @@ __global__ __launch_bounds__(DE_T) void depth_error_kernel(DepArgs a) {
   const bool group_ok = g >= 0 && g < d.n_groups;  // a view outside every group scores nothing
   if (!group_ok) g = 0;
   const double s = d.xform[2 * g], sh = d.xform[2 * g + 1];
-  for (int e = t; e < n_slots; e += DE_T) s_hist[e] = 0;
+  sr::hist_clear<DE_T>(s_hist, n_slots);
   __syncthreads();
   // n_valid, n_nonpos, n_invalid, rel, sq / g, sq, d, d^2, |d| / ln 10, delta 1..3, max rel
   double acc[NE];
@@ -462,7 +418,7 @@ __global__ __launch_bounds__(DE_T) void depth_error_kernel(DepArgs a) {
       acc[5] += sq;
       if (bits_finite(r_bits)) {
         if (rel > acc[12]) acc[12] = rel;
-        atomicAdd(&s_hist[rel_slot(r32, d.bin_len, d.n_bins)], 1u);
+        atomicAdd(&s_hist[sr::hist_slot(r32, d.bin_len, d.n_bins)], 1u);
       } else {
         atomicAdd(&s_hist[d.n_bins + 1], 1u);
       }
@@ -484,12 +440,8 @@ __global__ __launch_bounds__(DE_T) void depth_error_kernel(DepArgs a) {
     if (a.rel) reinterpret_cast<uint32_t*>(a.rel)[obase + i] = r_bits;
   }
   __syncthreads();
-  if (group_ok)
-    for (int e = t; e < n_slots; e += DE_T) {
-      const uint32_t c = s_hist[e];
-      if (c) atomicAdd(&d.hist[(int64_t)g * n_slots + e], c);
-    }
-  block_reduce<NE, true>(acc, s_red);
+  if (group_ok) sr::hist_flush<DE_T>(s_hist, d.hist + (int64_t)g * n_slots, n_slots);
+  sr::block_reduce<DE_T, NE, true>(acc, s_red);
   if (t == 0) {
     double* o = a.part_e + (int64_t)blockIdx.x * NE;
 #pragma unroll
@@ -559,18 +511,6 @@ bool dep_plan(int n_views, int64_t n_pix, int64_t stride, int n_groups, int rel_
   return true;
 }
 
-// positive and finite, on the bits (host code is built with -fno-honor-nans too)
-bool positive_finite(float x) {
-  uint32_t u;
-  memcpy(&u, &x, sizeof(u));
-  return u > 0u && u < 0x7f800000u;
-}
-bool is_nan(float x) {
-  uint32_t u;
-  memcpy(&u, &x, sizeof(u));
-  return (u & 0x7fffffffu) > 0x7f800000u;
-}
-
 }  // namespace
 
 extern "C" int64_t sr_select_workspace(int n_groups, int n_ranks) { return sel_workspace(n_groups, n_ranks); }
@@ -598,9 +538,7 @@ extern "C" int sr_select_ranks(sr_stream_t stream, const sr_select_desc* desc) {
            "sr_select_ranks: blocks_per_row %d outside [0, %d], or more than 2^31 - 1 workgroups", d.blocks_per_row,
            SEL_MAX_BPR);
   const int64_t need = sel_workspace(d.n_groups, d.n_ranks);
-  SR_CHECK(d.workspace_bytes >= need, SR_EINVAL, "sr_select_ranks: workspace of %lld bytes, %lld needed",
-           (long long)d.workspace_bytes, (long long)need);
-  SR_CHECK(((uintptr_t)d.workspace & 15) == 0, SR_EINVAL, "sr_select_ranks: the workspace must be 16-byte aligned");
+  SR_CHECK_WORKSPACE("sr_select_ranks", d.workspace, d.workspace_bytes, need);
   SelArgs a{};
   a.x = d.x, a.mask = d.mask, a.group = d.group;
   a.n_rows = d.n_rows, a.row_len = d.row_len, a.row_stride = d.row_stride;
@@ -634,18 +572,16 @@ extern "C" int sr_depth_eval(sr_stream_t stream, const sr_depth_eval_desc* desc)
            d.n_views);
   SR_CHECK(d.group || d.n_groups == d.n_views, SR_EINVAL, "sr_depth_eval: without group, n_groups must be n_views");
   SR_CHECK((d.conf != nullptr) == (d.conf_min != nullptr), SR_EINVAL, "sr_depth_eval: conf and conf_min go together");
-  SR_CHECK(!is_nan(d.gt_min) && !is_nan(d.gt_max) && d.gt_min < d.gt_max, SR_EINVAL,
+  SR_CHECK(!sr::is_nan(d.gt_min) && !sr::is_nan(d.gt_max) && d.gt_min < d.gt_max, SR_EINVAL,
            "sr_depth_eval: need gt_min < gt_max, neither a NaN");
   SR_CHECK(d.align >= SR_DEPTH_ALIGN_NONE && d.align <= SR_DEPTH_ALIGN_GIVEN, SR_EINVAL, "sr_depth_eval: unknown align %d",
            d.align);
   SR_CHECK(d.n_bins > 0 && d.n_bins <= MAX_BINS, SR_EINVAL, "sr_depth_eval: n_bins %d outside [1, %d]", d.n_bins, MAX_BINS);
-  SR_CHECK(positive_finite(d.bin_len), SR_EINVAL, "sr_depth_eval: bin_len must be positive and finite");
+  SR_CHECK(sr::positive_finite(d.bin_len), SR_EINVAL, "sr_depth_eval: bin_len must be positive and finite");
   DepPlan p;
   const int scratch = d.rel_q && !d.rel_err;
   SR_CHECK(dep_plan(d.n_views, d.n_pix, d.stride, d.n_groups, scratch, p), SR_EINVAL, "sr_depth_eval: no plan");
-  SR_CHECK(d.workspace_bytes >= p.bytes, SR_EINVAL, "sr_depth_eval: workspace of %lld bytes, %lld needed",
-           (long long)d.workspace_bytes, (long long)p.bytes);
-  SR_CHECK(((uintptr_t)d.workspace & 15) == 0, SR_EINVAL, "sr_depth_eval: the workspace must be 16-byte aligned");
+  SR_CHECK_WORKSPACE("sr_depth_eval", d.workspace, d.workspace_bytes, p.bytes);
   SR_CHECK(((uintptr_t)d.xform & 7) == 0 && ((uintptr_t)d.stats & 7) == 0, SR_EINVAL,
            "sr_depth_eval: fp64 buffers must be 8-byte aligned");
   char* ws = (char*)d.workspace;

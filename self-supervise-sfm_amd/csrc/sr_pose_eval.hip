@@ -35,12 +35,14 @@
 //                            poses staged in LDS, lane b of wave w keeps column b's poses in registers
 //                            and walks rows w, w + 4, ...; LDS histogram, one global atomic per used slot
 //   pose_pairs_list_kernel   the explicit list, 8 pairs per lane, poses gathered from global memory
-//   pose_align_kernel        one workgroup, three passes over the views (means, covariance, residuals)
-#include <string.h>
-
+//   pose_align_kernel        one workgroup, three passes over the views (means, covariance, residuals), each
+//                            summed by sr::block_reduce (sr_eval.h)
 #include "sr_common.h"
+#include "sr_eval.h"
 
 namespace {
+
+using sr::bits_nonfinite;
 
 constexpr int PE_T = 256;           // threads of every workgroup here
 constexpr int TILE = 64;            // views per tile side
@@ -48,9 +50,6 @@ constexpr int PSTR = 13;            // LDS floats per staged pose (12 + 1: odd s
 constexpr int MAX_BINS = 1024;
 constexpr int HROW = MAX_BINS + 2;  // LDS histogram row
 constexpr int LIST_RUN = 8;         // pairs per lane of the list kernel
-
-__device__ inline bool bits_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
-__device__ inline float quiet_nan() { return __uint_as_float(0x7fc00000u); }
 
 struct Pose {
   float r[9], t[3];
@@ -128,13 +127,6 @@ __device__ inline void pair_errors(const Pose& pr_i, const Pose& pr_j, const Pos
   trans = to_degrees(sqrtf(cx * cx + cy * cy + cz * cz), ambiguity ? fabsf(d) : d);
 }
 
-// slot of a finite, non-negative error: always in [0, n_bins]
-__device__ inline int err_slot(float err, float bin_deg, int n_bins) {
-  const float q = __fdiv_rn(err, bin_deg);
-  if (!(q < (float)n_bins)) return n_bins;
-  return min(max((int)q, 0), n_bins);
-}
-
 // Run-length front of one lane's LDS histogram adds: consecutive pairs mostly share a slot.
 struct SlotRun {
   int slot = -1;
@@ -168,20 +160,17 @@ __device__ inline PairOut score(bool bad, const Pose& pr_i, const Pose& pr_j, co
     bad = bits_nonfinite(o.rot) || bits_nonfinite(o.trans);
   }
   if (bad) {
-    o.rot = o.trans = quiet_nan();
+    o.rot = o.trans = sr::quiet_nan();
     o.s_rot = o.s_trans = o.s_max = d.n_bins + 1;
     return o;
   }
-  o.s_rot = err_slot(o.rot, d.bin_deg, d.n_bins);
-  o.s_trans = err_slot(o.trans, d.bin_deg, d.n_bins);
+  o.s_rot = sr::hist_slot(o.rot, d.bin_deg, d.n_bins);
+  o.s_trans = sr::hist_slot(o.trans, d.bin_deg, d.n_bins);
   o.s_max = max(o.s_rot, o.s_trans);  // the slot is monotone in the error
   return o;
 }
 
-__device__ inline void hist_clear(uint32_t* s_hist) {
-  for (int e = threadIdx.x; e < 3 * HROW; e += PE_T) s_hist[e] = 0;
-}
-
+// sr::hist_flush for three rows at once: HROW apart in LDS, packed in the global histogram
 __device__ inline void hist_flush(const uint32_t* s_hist, uint32_t* hist, int n_slots) {
   for (int e = threadIdx.x; e < 3 * n_slots; e += PE_T) {
     const int row = e / n_slots, k = e - row * n_slots;
@@ -203,7 +192,7 @@ __global__ __launch_bounds__(PE_T) void pose_pairs_tri_kernel(sr_pose_pairs_desc
   __shared__ int s_bad[2][TILE];            // per view of the i-tile / j-tile: a non-finite pose
   __shared__ uint32_t s_hist[3 * HROW];
   const int t = threadIdx.x, N = d.n_views, n_slots = d.n_bins + 2;
-  hist_clear(s_hist);
+  sr::hist_clear<PE_T>(s_hist, 3 * HROW);
   for (int e = t; e < 4 * TILE * 12; e += PE_T) {
     const int arr = e / (TILE * 12), rem = e - arr * (TILE * 12), v = rem / 12, c = rem - v * 12;
     const int view = ((arr & 2) ? tj : ti) * TILE + v;
@@ -256,7 +245,7 @@ __global__ __launch_bounds__(PE_T) void pose_pairs_tri_kernel(sr_pose_pairs_desc
 __global__ __launch_bounds__(PE_T) void pose_pairs_list_kernel(sr_pose_pairs_desc d) {
   __shared__ uint32_t s_hist[3 * HROW];
   const int t = threadIdx.x, N = d.n_views, n_slots = d.n_bins + 2;
-  hist_clear(s_hist);
+  sr::hist_clear<PE_T>(s_hist, 3 * HROW);
   __syncthreads();
   SlotRun run_rot, run_trans, run_max;
   const int64_t base = (int64_t)blockIdx.x * (LIST_RUN * PE_T);
@@ -298,25 +287,6 @@ __device__ inline void centre(const float* p, double c[3]) {
 #pragma unroll
   for (int a = 0; a < 3; ++a)
     c[a] = -((double)p[a] * (double)p[3] + (double)p[4 + a] * (double)p[7] + (double)p[8 + a] * (double)p[11]);
-}
-
-// sum of NV values over the workgroup, in a fixed tree; the result in every thread
-template <int NV>
-__device__ inline void block_sum(double (&v)[NV], double* smem) {
-  const int t = threadIdx.x;
-  __syncthreads();  // smem may still be read from the previous sum
-#pragma unroll
-  for (int e = 0; e < NV; ++e) smem[e * PE_T + t] = v[e];
-  __syncthreads();
-  for (int s = PE_T / 2; s > 0; s >>= 1) {
-    if (t < s) {
-#pragma unroll
-      for (int e = 0; e < NV; ++e) smem[e * PE_T + t] += smem[e * PE_T + t + s];
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int e = 0; e < NV; ++e) v[e] = smem[e * PE_T];
 }
 
 __device__ inline double dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
@@ -417,7 +387,7 @@ __global__ __launch_bounds__(PE_T) void pose_align_kernel(sr_pose_align_desc d) 
       acc[3 + a] += g[a] - g0[a];
     }
   }
-  block_sum(acc, s_red);
+  sr::block_reduce<PE_T>(acc, s_red);
   for (int e = 0; e < 6; ++e) acc[e] /= (double)N;
   double mp[3], mg[3];
   for (int a = 0; a < 3; ++a) {
@@ -439,7 +409,7 @@ __global__ __launch_bounds__(PE_T) void pose_align_kernel(sr_pose_align_desc d) 
       for (int c = 0; c < 3; ++c) cov[3 * r + c] += g[r] * p[c];
     cov[9] += dot3(p, p);
   }
-  block_sum(cov, s_red);
+  sr::block_reduce<PE_T>(cov, s_red);
   for (int e = 0; e < 10; ++e) cov[e] /= (double)N;
   if (t == 0) {
     double R[9], sigma_sum, scale = 1.0;
@@ -472,18 +442,11 @@ __global__ __launch_bounds__(PE_T) void pose_align_kernel(sr_pose_align_desc d) 
     sq[0] += e2;
     if (d.err) d.err[k] = sqrt(e2);
   }
-  block_sum(sq, s_red);
+  sr::block_reduce<PE_T>(sq, s_red);
   if (t == 0) d.out[13] = sqrt(sq[0] / (double)N);
 }
 
 bool stride_ok(int s) { return s == 12 || s == 16; }
-
-// positive and finite, on the bits (host code is built with -fno-honor-nans too)
-bool positive_finite(float x) {
-  uint32_t u;
-  memcpy(&u, &x, sizeof(u));
-  return u > 0u && u < 0x7f800000u;
-}
 
 }  // namespace
 
@@ -497,7 +460,7 @@ extern "C" int sr_pose_pair_errors(sr_stream_t stream, const sr_pose_pairs_desc*
            "sr_pose_pair_errors: strides %d / %d must be 12 or 16 floats", d.pred_stride, d.gt_stride);
   SR_CHECK(d.n_bins > 0 && d.n_bins <= MAX_BINS, SR_EINVAL, "sr_pose_pair_errors: n_bins %d outside [1, %d]", d.n_bins,
            MAX_BINS);
-  SR_CHECK(positive_finite(d.bin_deg), SR_EINVAL, "sr_pose_pair_errors: bin_deg must be positive and finite");
+  SR_CHECK(sr::positive_finite(d.bin_deg), SR_EINVAL, "sr_pose_pair_errors: bin_deg must be positive and finite");
   SR_CHECK((d.pair_i != nullptr) == (d.pair_j != nullptr), SR_EINVAL,
            "sr_pose_pair_errors: pair_i and pair_j go together");
   SR_CHECK(!d.pair_i || d.n_pairs > 0, SR_EINVAL, "sr_pose_pair_errors: a pair list of %d entries", d.n_pairs);

@@ -17,7 +17,7 @@
 //                        to the LDS histogram (an integer count: the order of the adds is immaterial).
 //                        Each workgroup then adds its 256 counts to the pass's digit totals.
 //   sort_scan_kernel     one workgroup per digit d: base = the sum of the totals of the digits below d,
-//                        then the exclusive scan of row d of the table, in place.  The table is
+//                        then the exclusive scan of row d of the table, in place (sr::scan_row).  The table is
 //                        digit-major, so this is the exclusive scan of the whole [256][tiles] table.
 //                        Every workgroup works from the totals alone: none waits for another.
 //   sort_scatter_kernel  a lane's rank among its tile's equal digits = (the count of the digit in the
@@ -27,6 +27,7 @@
 //   Passes ping-pong between two buffers of the workspace; the first reads the inputs, the last writes
 //   the outputs.
 #include "sr_common.h"
+#include "sr_eval.h"
 
 namespace {
 
@@ -38,7 +39,7 @@ constexpr int ST_TILE = ST_T * ST_ROUNDS;  // 2048
 constexpr int ST_MAX_PASSES = 8;
 constexpr int64_t ST_MAX_N = 2147483647LL;
 
-inline int64_t align16(int64_t b) { return (b + 15) & ~int64_t(15); }
+using sr::align16;
 
 struct SortPlan {
   int64_t tiles;
@@ -111,7 +112,6 @@ __global__ __launch_bounds__(ST_T) void sort_hist_kernel(SortArgs a) {
 // grid 256: workgroup d scans row d of the table in place, starting from the totals of the digits below d
 __global__ __launch_bounds__(ST_T) void sort_scan_kernel(SortArgs a) {
   __shared__ uint32_t s_scan[ST_T];
-  __shared__ uint32_t s_carry;
   const int t = threadIdx.x, d = blockIdx.x;
   s_scan[t] = t < d ? a.totals[t] : 0u;
   __syncthreads();
@@ -119,34 +119,9 @@ __global__ __launch_bounds__(ST_T) void sort_scan_kernel(SortArgs a) {
     if (t < s) s_scan[t] += s_scan[t + s];
     __syncthreads();
   }
-  if (t == 0) s_carry = s_scan[0];
-  __syncthreads();
+  const uint32_t base = s_scan[0];  // read by every lane before scan_row's first barrier lets s_scan be written
   uint32_t* row = a.table + (int64_t)d * a.tiles;
-  for (int64_t c0 = 0; c0 < a.tiles; c0 += 4 * ST_T) {
-    const int64_t e0 = c0 + 4 * t;
-    uint32_t v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = e0 + u < a.tiles ? row[e0 + u] : 0u;
-    const uint32_t mine = v[0] + v[1] + v[2] + v[3];
-    const uint32_t carry = s_carry;
-    s_scan[t] = mine;
-    __syncthreads();
-    for (int off = 1; off < ST_T; off <<= 1) {
-      const uint32_t o = t >= off ? s_scan[t - off] : 0u;
-      __syncthreads();
-      s_scan[t] += o;
-      __syncthreads();
-    }
-    uint32_t run = carry + s_scan[t] - mine;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      if (e0 + u < a.tiles) row[e0 + u] = run;
-      run += v[u];
-    }
-    __syncthreads();  // every lane has read the carry and the scan
-    if (t == ST_T - 1) s_carry = carry + s_scan[t];
-    __syncthreads();
-  }
+  sr::scan_row<ST_T>(a.tiles, base, s_scan, [&](int64_t e) { return row[e]; }, [&](int64_t e, uint32_t x) { row[e] = x; });
 }
 
 __global__ __launch_bounds__(ST_T) void sort_scatter_kernel(SortArgs a) {
@@ -259,9 +234,7 @@ extern "C" int sr_sort_pairs(sr_stream_t stream, const sr_sort_desc* desc) {
   SR_CHECK(((uintptr_t)d.vals_in & 3) == 0 && ((uintptr_t)d.vals_out & 3) == 0, SR_EINVAL,
            "sr_sort_pairs: values must be 4-byte aligned");
   const int64_t need = sr::sort_workspace(d.n);
-  SR_CHECK(d.workspace_bytes >= need, SR_EINVAL, "sr_sort_pairs: workspace of %lld bytes, %lld needed",
-           (long long)d.workspace_bytes, (long long)need);
-  SR_CHECK(((uintptr_t)d.workspace & 15) == 0, SR_EINVAL, "sr_sort_pairs: the workspace must be 16-byte aligned");
+  SR_CHECK_WORKSPACE("sr_sort_pairs", d.workspace, d.workspace_bytes, need);
   sr::sort_launch((hipStream_t)stream, d.keys_in, d.vals_in, d.keys_out, d.vals_out, d.n, d.key_bits, d.workspace);
   sr::note_kernel("sort_scatter_kernel");
   return sr::check_launch("sr_sort_pairs");

@@ -20,12 +20,12 @@
 //   sr::sort_launch         twice, on 32 + bit_length(n_groups) bits.  Order C carries the err bits as its
 //                           value; order O's err is read back from the low word of its sorted key.  Both
 //                           reductions stream contiguous memory.
-//   sparsify_scan_kernel    one workgroup: the exclusive scans of the considered counts (group starts) and of
-//                           K split_g (the first reduction workgroup of every group)
+//   sparsify_scan_kernel    one workgroup: the exclusive scans (sr::scan_row) of the considered counts (group
+//                           starts) and of K split_g (the first reduction workgroup of every group)
 //   sparsify_reduce_kernel  workgroup w of order c finds its group by bisection of the second scan, then its
 //                           bin and its chunk of 4096 positions: a lane's elements ascending (stride 256),
-//                           a fixed LDS tree, one partial.  split_g = max(1, ceil(ceil(n / K) / 4096)) chunks
-//                           per bin, the same for every bin of a group, so a long bin is spread over many
+//                           sr::block_reduce's fixed tree, one partial.  split_g = max(1, ceil(ceil(n / K) / 4096))
+//                           chunks per bin, the same for every bin of a group, so a long bin is spread over many
 //                           workgroups and the grid is known on the host: at most N / 4096 + 2 G K.
 //   sparsify_finish_kernel  one wave per (group, bin): the partials of the bin, a lane's ascending (stride
 //                           64), then a fixed shuffle tree; cut from the sorted key of order C; the counts.
@@ -33,6 +33,7 @@
 // The Makefile builds this file with -ffp-contract=off -fhonor-nans: under -fno-honor-nans the compiler reads
 // the test on the exponent bits as a float classification and reduces it to |x| == Inf, which a NaN fails.
 #include "sr_common.h"
+#include "sr_eval.h"
 
 namespace {
 
@@ -44,11 +45,10 @@ constexpr int64_t SP_MAX_N = 2147483647LL;
 constexpr int SP_MAX_GROUPS = 65535;
 constexpr int SP_MAX_STEPS = 1024;
 
-inline int64_t align16(int64_t b) { return (b + 15) & ~int64_t(15); }
-
-__device__ inline bool bits_nonfinite(uint32_t b) { return (b & 0x7f800000u) == 0x7f800000u; }
-__device__ inline uint32_t key32(uint32_t b) { return b ^ ((b & 0x80000000u) ? 0xffffffffu : 0x80000000u); }
-__device__ inline uint32_t unkey32(uint32_t k) { return (k & 0x80000000u) ? k ^ 0x80000000u : ~k; }
+using sr::align16;
+using sr::bits_nonfinite;
+using sr::key32;
+using sr::unkey32;
 
 struct SpPlan {
   int64_t n;        // n_rows * row_len
@@ -161,45 +161,13 @@ __global__ __launch_bounds__(SP_T) void sparsify_key_kernel(SpArgs a) {
   if (t < 2 && s_cnt[t]) atomicAdd(&a.gcnt[2 * g0 + t], s_cnt[t]);  // s_cnt != 0: g0 is in range
 }
 
-// exclusive scan of one value per thread over the workgroup; the total in every thread's `total`
-__device__ inline uint32_t block_exclusive(uint32_t v, uint32_t* smem, uint32_t& total) {
-  const int t = threadIdx.x;
-  __syncthreads();
-  smem[t] = v;
-  __syncthreads();
-  for (int off = 1; off < SP_T; off <<= 1) {
-    const uint32_t o = t >= off ? smem[t - off] : 0u;
-    __syncthreads();
-    smem[t] += o;
-    __syncthreads();
-  }
-  total = smem[SP_T - 1];
-  return smem[t] - v;
-}
-
 __global__ __launch_bounds__(SP_T) void sparsify_scan_kernel(SpArgs a) {
   __shared__ uint32_t s_scan[SP_T];
-  const int t = threadIdx.x, G = a.d.n_groups, K = a.d.n_steps;
-  uint32_t carry_n = 0, carry_w = 0;
-  for (int c0 = 0; c0 < G; c0 += 4 * SP_T) {
-    const int e0 = c0 + 4 * t;
-    uint32_t cn[4], cw[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      cn[u] = e0 + u < G ? a.gcnt[2 * (e0 + u)] : 0u;
-      cw[u] = e0 + u < G ? (uint32_t)K * split_of(cn[u], K) : 0u;
-    }
-    uint32_t total_n, total_w;
-    uint32_t run_n = carry_n + block_exclusive(cn[0] + cn[1] + cn[2] + cn[3], s_scan, total_n);
-    uint32_t run_w = carry_w + block_exclusive(cw[0] + cw[1] + cw[2] + cw[3], s_scan, total_w);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      if (e0 + u < G) a.gstart[e0 + u] = run_n, a.wstart[e0 + u] = run_w;
-      run_n += cn[u], run_w += cw[u];
-    }
-    carry_n += total_n, carry_w += total_w;
-  }
-  if (t == 0) a.wstart[G] = carry_w;
+  const int G = a.d.n_groups, K = a.d.n_steps;
+  sr::scan_row<SP_T>(G, 0u, s_scan, [&](int g) { return a.gcnt[2 * g]; }, [&](int g, uint32_t x) { a.gstart[g] = x; });
+  const uint32_t wgs = sr::scan_row<SP_T>(G, 0u, s_scan, [&](int g) { return (uint32_t)K * split_of(a.gcnt[2 * g], K); },
+                                          [&](int g, uint32_t x) { a.wstart[g] = x; });
+  if (threadIdx.x == 0) a.wstart[G] = wgs;
 }
 
 // grid (wgs, 2): workgroup w of order c sums one chunk of one bin
@@ -221,18 +189,13 @@ __global__ __launch_bounds__(SP_T) void sparsify_reduce_kernel(SpArgs a) {
   int64_t p1 = (int64_t)a.gstart[g] + b1;
   if (p1 > p0 + SP_CHUNK) p1 = p0 + SP_CHUNK;
   if (p1 > a.n) p1 = a.n;  // always: start + n <= the element count
-  double sum = 0.0;
+  double sum[1] = {0.0};
   for (int64_t p = p0 + t; p < p1; p += SP_T) {
     const uint32_t eb = order == 0 ? a.sval[p] : unkey32(~(uint32_t)a.keyc[p]);
-    sum += (double)__uint_as_float(eb);
+    sum[0] += (double)__uint_as_float(eb);
   }
-  s_sum[t] = sum;
-  __syncthreads();
-  for (int off = SP_T / 2; off > 0; off >>= 1) {
-    if (t < off) s_sum[t] += s_sum[t + off];
-    __syncthreads();
-  }
-  if (t == 0) a.part[(int64_t)order * a.wgs + w] = s_sum[0];
+  sr::block_reduce<SP_T>(sum, s_sum);
+  if (t == 0) a.part[(int64_t)order * a.wgs + w] = sum[0];
 }
 
 // one wave per (group, bin)
@@ -255,7 +218,7 @@ __global__ __launch_bounds__(SP_T) void sparsify_finish_kernel(SpArgs a) {
   }
   if (lane != 0) return;
   if (d.cut) {
-    uint32_t bits = 0x7fc00000u;
+    uint32_t bits = sr::QNAN_BITS;
     const int64_t p = (int64_t)a.gstart[g] + (int64_t)k * n / K;
     if (n > 0 && p < a.n) {
       const uint32_t low = (uint32_t)a.skeyc[p];
@@ -294,9 +257,7 @@ extern "C" int sr_sparsify(sr_stream_t stream, const sr_sparsify_desc* desc) {
            "sr_sparsify: unknown order %d", d.order);
   SpPlan p;
   sp_plan(d.n_rows, d.row_len, d.n_groups, d.n_steps, p);
-  SR_CHECK(d.workspace_bytes >= p.bytes, SR_EINVAL, "sr_sparsify: workspace of %lld bytes, %lld needed",
-           (long long)d.workspace_bytes, (long long)p.bytes);
-  SR_CHECK(((uintptr_t)d.workspace & 15) == 0, SR_EINVAL, "sr_sparsify: the workspace must be 16-byte aligned");
+  SR_CHECK_WORKSPACE("sr_sparsify", d.workspace, d.workspace_bytes, p.bytes);
   SR_CHECK(((uintptr_t)d.bin_sum & 7) == 0, SR_EINVAL, "sr_sparsify: bin_sum must be 8-byte aligned");
   char* ws = (char*)d.workspace;
   a.keyc = (uint64_t*)(ws + p.off_keyc);

@@ -64,6 +64,19 @@ def test_sort_is_the_stable_argsort(key_bits):
                 assert np.array_equal(sv3, sv) and np.array_equal(sk3, sk), (n, kind, "second run")
 
 
+# 1025 tiles: the rows that sort_scan_kernel and voxel_head_scan_kernel scan in chunks of 4 x 256 values enter a
+# second chunk, whose results depend on the carry out of the first
+CARRY_N = 1024 * R.TILE + 1
+
+
+def test_sort_carries_into_the_second_chunk_of_the_table_scan():
+    keys = R.sort_keys("random", CARRY_N, 40)
+    ref = R.sort_ref(keys, 40)
+    sk, perm = gpu_sort(keys, 40)
+    assert np.array_equal(perm, ref), "permutation"
+    assert np.array_equal(sk, keys[ref]), "keys: bits above key_bits ride along"
+
+
 def test_sort_rejections_surface_as_errors():
     from sailrecon_amd import ops
     from sailrecon_amd._lib import SfmAmdError
@@ -169,6 +182,14 @@ def test_sizes(n):
                   mode=mode)
         want = R.downsample(p, voxel, **kw)
         compare(gpu_voxel(p, voxel, extra=8, **kw), want, 4, (n, mode))
+
+
+def test_head_scan_carries_into_the_second_chunk():
+    """CARRY_N points in about 1.6 million voxels: the last tile's base and the voxel count come through the carry."""
+    p = np.random.default_rng(2023).uniform(-4, 4, (CARRY_N, 3)).astype(np.float32)
+    want = R.downsample(p, 0.05)
+    assert want["counts"][0] > 2 ** 20 and want["counts"][1] == CARRY_N
+    compare(gpu_voxel(p, 0.05, extra=8), want, 0, "second chunk")
 
 
 def test_every_optional_output_may_be_absent():

@@ -147,6 +147,16 @@ def test_multi_tile_sorts_and_split_bins(K):
             print(f"70001, K {K}, {order}, {kind}: worst bin-sum error {worst:.2e} of fsum(|v|) (bound {SUM_TOL})")
 
 
+def test_group_scan_carries_into_the_second_chunk():
+    """1025 rows of 8 as 1025 groups: sparsify_scan_kernel scans the group counts in chunks of 4 x 256, and the
+    last group's start and first workgroup come through the carry out of the first chunk."""
+    for kind in ("int", "real"):
+        err, conf, mask = make(1025, 8, kind, 77, kind == "real")
+        want = R.sparsify(err, conf, 4, mask=mask)
+        assert want["count"][1024, 0] > 0
+        compare(gpu(err, conf, 4, mask=mask), want, ("second chunk", kind), kind == "int")
+
+
 @pytest.mark.parametrize("name", R.CASES)
 def test_golden_cases(name):
     """Every golden case and configuration, against the restatement and against the stored answers."""
