@@ -389,7 +389,7 @@ def _uv_pos_embed(h: int, w: int, c: int, aspect: float) -> Tensor:
 
 
 def _add_pos(x: Tensor, aspect: float, ratio: float = 0.1) -> Tensor:  # x NCHW
-    pe = _uv_pos_embed(x.shape[2], x.shape[3], x.shape[1], aspect) * ratio
+    pe = _uv_pos_embed(x.shape[2], x.shape[3], x.shape[1], aspect).to(x.dtype) * ratio
     return x + pe.permute(2, 0, 1)[None]
 
 
@@ -422,11 +422,15 @@ def _fusion(sd: SD, pre: str, x0: Tensor, x1: Optional[Tensor], size) -> Tensor:
 
 def dpt_forward(sd: SD, pre: str, tokens: Dict[int, Tensor], images: Tensor, patch_start: int,
                 layers: Sequence[int] = (4, 11, 17, 23), activation: str = "inv_log",
-                conf_activation: str = "expp1", patch: int = 14, feature_only: bool = False):
-    """DPTHead.forward (dpt_head.py:151-298) for all frames at once; returns (preds, conf), or with
-    feature_only the fused feature map [B, S, features, H, W] (dpt_head.py:123-126,286-287)."""
+                conf_activation: str = "expp1", patch: int = 14, feature_only: bool = False,
+                pos_embed: bool = True, down_ratio: int = 1):
+    """DPTHead.forward (dpt_head.py:151-298) for all frames at once; returns (preds [B,S,oh,ow,C-1],
+    conf [B,S,oh,ow]), or with feature_only the fused feature map [B, S, features, oh, ow]
+    (dpt_head.py:123-126,286-287); oh = int((H // patch) * patch / down_ratio), ow likewise
+    (dpt_head.py:273-281).  Runs in the dtype of its inputs (fp32, or fp64 as the tests' oracle)."""
     B, S, _, H, W = images.shape
     ph, pw = H // patch, W // patch
+    oh, ow = int(ph * patch / down_ratio), int(pw * patch / down_ratio)
     aspect = W / H
     feats = []
     for i, l in enumerate(layers):
@@ -434,7 +438,8 @@ def dpt_forward(sd: SD, pre: str, tokens: Dict[int, Tensor], images: Tensor, pat
         x = layer_norm(x, sd[pre + "norm.weight"], sd[pre + "norm.bias"], 1e-5)
         x = x.permute(0, 2, 1).reshape(B * S, -1, ph, pw)
         x = _conv(sd, pre + f"projects.{i}", x)
-        x = _add_pos(x, aspect)
+        if pos_embed:
+            x = _add_pos(x, aspect)
         rp = pre + f"resize_layers.{i}"
         if i in (0, 1):
             x = F.conv_transpose2d(x, sd[rp + ".weight"], sd[rp + ".bias"], stride=4 if i == 0 else 2)
@@ -447,8 +452,9 @@ def dpt_forward(sd: SD, pre: str, tokens: Dict[int, Tensor], images: Tensor, pat
     out = _fusion(sd, pre + "scratch.refinenet2", out, rn[1], rn[0].shape[2:])
     out = _fusion(sd, pre + "scratch.refinenet1", out, rn[0], None)
     out = _conv(sd, pre + "scratch.output_conv1", out)
-    out = F.interpolate(out, size=(ph * patch, pw * patch), mode="bilinear", align_corners=True)
-    out = _add_pos(out, aspect)
+    out = F.interpolate(out, size=(oh, ow), mode="bilinear", align_corners=True)
+    if pos_embed:
+        out = _add_pos(out, aspect)
     if feature_only:
         return out.view(B, S, *out.shape[1:])
     out = F.relu(_conv(sd, pre + "scratch.output_conv2.0", out))
@@ -459,10 +465,21 @@ def dpt_forward(sd: SD, pre: str, tokens: Dict[int, Tensor], images: Tensor, pat
         pts = torch.sign(xyz) * torch.expm1(xyz.abs())
     elif activation == "exp":
         pts = xyz.exp()
+    elif activation == "relu":
+        pts = F.relu(xyz)
+    elif activation == "linear":
+        pts = xyz
     else:
         raise ValueError(activation)
-    conf = 1 + cf.exp() if conf_activation == "expp1" else cf.exp()
-    return pts.reshape(B, S, H, W, -1), conf.reshape(B, S, H, W)
+    if conf_activation == "expp1":  # head_act.py:105-112
+        conf = 1 + cf.exp()
+    elif conf_activation == "expp0":
+        conf = cf.exp()
+    elif conf_activation == "sigmoid":
+        conf = torch.sigmoid(cf)
+    else:
+        raise ValueError(conf_activation)
+    return pts.reshape(B, S, oh, ow, -1), conf.reshape(B, S, oh, ow)
 
 
 def unproject_depth(depth: Tensor, extr: Tensor, intr: Tensor) -> Tensor:

@@ -73,6 +73,11 @@ __global__ void convt_scatter_kernel(const float* __restrict__ g, int n, int h, 
 }
 
 // ---------------------------------------------------------------- bilinear resize
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;  // never one half of an FMA
+}
+
 // F.interpolate(mode="bilinear", align_corners=True) (custom_interpolate, dpt_head.py:568-598):
 // src = dst * (in - 1) / (out - 1); weights and blend in PyTorch's order.  Optional `add`
 // (same shape as out) is summed after interpolation.
@@ -89,7 +94,10 @@ __global__ void resize_bilinear_kernel(const float* __restrict__ x, int n, int h
     const int64_t r = p / wo;
     const int oy = (int)(r % ho);
     const int f = (int)(r / ho);
-    const float fy = sy * oy, fx = sx * ox;
+    // the source coordinate is rounded to fp32 before the weights are taken from it (PyTorch's
+    // definition): contracted into fma(sx, ox, -x0) the weight moves by the coordinate's rounding
+    // error, up to 2^-24 times the coordinate, and the result by that times |b - a|
+    const float fy = mul_rounded(sy, (float)oy), fx = mul_rounded(sx, (float)ox);
     const int y0 = (int)fy, x0 = (int)fx;
     const int y1 = y0 + (y0 < h - 1), x1 = x0 + (x0 < w - 1);
     const float ly1 = fy - y0, ly0 = 1.f - ly1, lx1 = fx - x0, lx0 = 1.f - lx1;

@@ -7,13 +7,13 @@ sail_recon.py:118), with feature maps in NHWC:
 
     tokens --LN (row map skips the 5 special tokens)--> 1x1 conv (GEMM) -> + uv pos-embed
       -> resize: ConvTranspose k4 / k2 (GEMM + scatter) | identity | 3x3 stride-2 conv
-    layer*_rn 3x3 convs (im2col + GEMM) -> refinenet4..1 (ResidualConvUnits: ReLU fused into
-      im2col, residual via the GEMM's gamma*(acc+bias) epilogue with gamma = 1; bilinear
+    layer*_rn 3x3 convs (implicit GEMM) -> refinenet4..1 (ResidualConvUnits: ReLU fused into
+      the conv's operand read, residual via the gamma*(acc+bias) epilogue with gamma = 1; bilinear
       align_corners resize; 1x1 out_conv)
     output_conv1 (3x3) -> bilinear to the image size -> + pos-embed -> output_conv2[0] (3x3)
     -> ReLU + 1x1 + activate_head fused (sr_dpt_head_out_f32)
 
-Frames are processed in chunks sized to bound the largest im2col buffer; results do not
+Frames are processed in chunks sized to bound one chunk's activations; results do not
 depend on the chunking (every op is per frame), exactly as for the reference's
 frames_chunk_size.
 """
@@ -29,7 +29,6 @@ from .. import _lib, ops, runtime
 
 Tensor = torch.Tensor
 
-IM2COL_BUDGET = 2 << 30  # bytes: largest im2col buffer per chunk (convs with C % 32 != 0 only)
 ACT_BUDGET = 16 << 30    # bytes: activations of one chunk of frames (implicit-GEMM convs)
 
 
@@ -73,6 +72,13 @@ class DPTHead(nn.Module):
         super().__init__()
         if activation not in ops.DPT_ACT or conf_activation not in ops.DPT_CONF_ACT:
             raise ValueError(f"unsupported activation {activation!r} / {conf_activation!r}")
+        # every conv is a GEMM over channels: K tiles hold 32 fp32 channels (sr_conv3x3_f32, sr_gemm)
+        widths = {"dim_in": dim_in, "features": features, "features // 2": features // 2}
+        widths.update({f"out_channels[{i}]": c for i, c in enumerate(out_channels)})
+        bad = {k: v for k, v in widths.items() if v <= 0 or v % 32 != 0}
+        if bad or output_dim < 2:
+            raise ValueError("DPTHead supports dim_in, out_channels, features and features // 2 that are multiples "
+                             f"of 32 and output_dim >= 2; got {bad or dict(output_dim=output_dim)}")
         self.patch_size = patch_size
         self.activation = activation
         self.conf_activation = conf_activation
@@ -163,29 +169,16 @@ class DPTHead(nn.Module):
     def _conv3x3(self, x: Tensor, name: str, conv: nn.Conv2d, stride: int = 1, relu_in: bool = False,
                  out: Tensor = None, resid: bool = False) -> Tensor:
         """3x3 / pad 1 conv of NHWC x; resid: out += conv(x) (+ bias) instead of out = ...
-        C % 32 == 0 (every conv of the default heads): implicit GEMM (sr_conv3x3_f32, nothing
-        materialised); otherwise im2col + GEMM."""
+        Implicit GEMM (sr_conv3x3_f32, nothing materialised): the constructor admits only widths it
+        supports (C % 32 == 0)."""
         n, h, w, c = x.shape
         ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
         cout = conv.weight.shape[0]
-        if c % 32 == 0 and cout % 4 == 0:
-            if out is None:
-                out = torch.empty(n, ho, wo, cout, device=x.device, dtype=torch.float32)
-            bias = None if conv.bias is None else self._pk(name + ".bias", lambda: conv.bias)
-            ops.conv3x3(x, self._conv_w(name, conv), out, stride=stride, relu_in=relu_in, bias=bias,
-                        resid_gamma=self._ones_for(cout, x.device) if resid else None, tag="dpt_conv3x3")
-            return out
-        cols = torch.empty(n * ho * wo, 9 * c, device=x.device, dtype=torch.float32)
-        ops.im2col3x3(x, stride, relu_in, cols)
-        cout = conv.weight.shape[0]
         if out is None:
             out = torch.empty(n, ho, wo, cout, device=x.device, dtype=torch.float32)
-        wt = self._conv_w(name, conv)
-        if resid:
-            self._gemm(cols, wt, conv.bias, out.view(-1, cout), _lib.SR_EPI_BIAS_RESID,
-                       gamma=self._ones_for(cout, x.device))
-        else:
-            self._gemm(cols, wt, conv.bias, out.view(-1, cout))
+        bias = None if conv.bias is None else self._pk(name + ".bias", lambda: conv.bias)
+        ops.conv3x3(x, self._conv_w(name, conv), out, stride=stride, relu_in=relu_in, bias=bias,
+                    resid_gamma=self._ones_for(cout, x.device) if resid else None, tag="dpt_conv3x3")
         return out
 
     def _conv1x1(self, x: Tensor, name: str, conv: nn.Conv2d) -> Tensor:
@@ -218,11 +211,19 @@ class DPTHead(nn.Module):
         return self._conv1x1(up, name + ".out_conv", blk.out_conv)
 
     # ------------------------------------------------------------------ forward
+    @staticmethod
+    def frame_bytes(f: int, ph: int, pw: int, oh: int, ow: int) -> int:
+        """Activation bytes of one frame, which bound a chunk (ACT_BUDGET): the upsampled
+        output_conv1 map + output_conv2's hidden map at oh x ow, the refinenet1 maps at 8x."""
+        return oh * ow * (f // 2 + 2 * (f // 8)) * 4 + (8 * ph) * (8 * pw) * f * 4 * 3
+
     def forward(self, aggregated_tokens_list: Union[List[Tensor], Dict[int, Tensor]], images: Tensor,
                 patch_start_idx: int, frames_chunk_size: int = 8) -> Union[Tensor, Tuple[Tensor, Tensor]]:
-        """dpt_head.py:151-229: returns (preds [B,S,H,W,output_dim-1], conf [B,S,H,W]) fp32, or with
-        feature_only the fused feature map [B, S, features, H', W'] (dpt_head.py:286-287; an NCHW
-        view of the NHWC map the kernels write, no copy).  ``frames_chunk_size`` is accepted for
+        """dpt_head.py:151-229: returns (preds [B,S,oh,ow,output_dim-1], conf [B,S,oh,ow]) fp32, or with
+        feature_only the fused feature map [B, S, features, oh, ow] (dpt_head.py:286-287; an NCHW
+        view of the NHWC map the kernels write, no copy), where oh = int((H // patch) * patch /
+        down_ratio) and ow likewise (dpt_head.py:273-281): H x W only when both are multiples of the
+        patch size and down_ratio is 1.  ``frames_chunk_size`` is accepted for
         signature parity; chunking here is sized by memory."""
         B, S, _, H, W = images.shape
         runtime.require_device(images, "DPTHead")
@@ -236,18 +237,9 @@ class DPTHead(nn.Module):
             preds = torch.empty(frames, oh, ow, f, device=dev, dtype=torch.float32)
             conf = None
         else:
-            preds = torch.empty(B, S, H, W, self.output_dim - 1, device=dev, dtype=torch.float32)
-            conf = torch.empty(B, S, H, W, device=dev, dtype=torch.float32)
-        convs3 = [m for m in self.modules() if isinstance(m, nn.Conv2d) and m.kernel_size == (3, 3)]
-        if all(m.in_channels % 32 == 0 and m.out_channels % 4 == 0 for m in convs3):
-            # implicit-GEMM convs: the chunk is bounded by its activations (largest: the upsampled
-            # output_conv1 map + output_conv2's hidden map at oh x ow, the refinenet1 maps at 8x)
-            per_frame = oh * ow * (f // 2 + 2 * (f // 8)) * 4 + (8 * ph) * (8 * pw) * f * 4 * 3
-            chunk = max(1, min(frames, ACT_BUDGET // per_frame))
-        else:
-            per_frame = max(oh * ow * 9 * (self.scratch.output_conv1.weight.shape[0]) * 4,
-                            (4 * ph) * (4 * pw) * 9 * self.scratch.layer1_rn.weight.shape[1] * 4)
-            chunk = max(1, min(frames, IM2COL_BUDGET // per_frame))
+            preds = torch.empty(B, S, oh, ow, self.output_dim - 1, device=dev, dtype=torch.float32)
+            conf = torch.empty(B, S, oh, ow, device=dev, dtype=torch.float32)
+        chunk = max(1, min(frames, ACT_BUDGET // self.frame_bytes(f, ph, pw, oh, ow)))
         toks = []
         for layer_idx in self.intermediate_layer_idx:
             t = aggregated_tokens_list[layer_idx]
@@ -263,7 +255,7 @@ class DPTHead(nn.Module):
                     self._forward_chunk(toks, P, patch_start_idx, f0, f1, ph, pw, H, W, oh, ow, preds[f0:f1], None)
                 else:
                     self._forward_chunk(toks, P, patch_start_idx, f0, f1, ph, pw, H, W, oh, ow,
-                                        preds.view(frames, H, W, -1)[f0:f1], conf.view(frames, H, W)[f0:f1])
+                                        preds.view(frames, oh, ow, -1)[f0:f1], conf.view(frames, oh, ow)[f0:f1])
         if self.feature_only:
             return preds.view(B, S, oh, ow, f).permute(0, 1, 4, 2, 3)
         return preds, conf

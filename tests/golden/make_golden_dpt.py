@@ -17,6 +17,10 @@ DPTHead's own state_dict keys.  Inputs: seeded randn tokens / rand images.
   g6_dpt_feat_small.npz  DPTHead(SMALL, feature_only=True) (dpt_head.py:123-126,286-287):
                      the fused feature map [1, S, 64, H, W], frames_chunk_size=2
                      (``--only feature`` writes this file alone)
+  g6_dpt_variants.npz  DPTHead(SMALL, output_dim=2, ...) at S=2 on 60x75 images (not multiples of
+                     14: 4x5 patches, maps of 56x70) for default / down_ratio=2 / pos_embed=False /
+                     (linear, sigmoid) / (relu, expp0): the paths and the output shape the other
+                     files do not reach (``--only variants`` writes this file alone)
 """
 
 from __future__ import annotations
@@ -71,6 +75,32 @@ def feature_only():
     for l, t in toks.items():
         out[f"tok_{l}"] = t.numpy()
     np.savez(os.path.join(HERE, "g6_dpt_feat_small.npz"), **out)
+
+
+VARIANTS = {"default": dict(), "down2": dict(down_ratio=2), "nopos": dict(pos_embed=False),
+            "linear_sigmoid": dict(activation="linear", conf_activation="sigmoid"),
+            "relu_expp0": dict(activation="relu", conf_activation="expp0")}
+
+
+def variants():
+    S, H, W = 2, 60, 75
+    P = 5 + (H // 14) * (W // 14)
+    toks = tokens_for(SMALL["intermediate_layer_idx"], S, P, SMALL["dim_in"], 7)
+    images = torch.rand(1, S, 3, H, W, generator=torch.Generator().manual_seed(8))
+    out = dict(images=images.numpy())
+    for l, t in toks.items():
+        out[f"tok_{l}"] = t.numpy()
+    with torch.no_grad():
+        for name, kw in VARIANTS.items():
+            m = DPTHead(**SMALL, output_dim=2, **kw).eval()  # inv_log / expp1 unless the variant says otherwise
+            m.load_state_dict(synth_state_dict_like(m))
+            preds, conf = m(toks, images=images, patch_start_idx=5)
+            out[f"{name}_preds"] = preds.numpy()
+            out[f"{name}_conf"] = conf.numpy()
+            print(name, tuple(preds.shape), tuple(conf.shape))
+    path = os.path.join(HERE, "g6_dpt_variants.npz")
+    np.savez(path, **out)
+    print("g6_dpt_variants.npz", os.path.getsize(path) // 1024, "KiB")
 
 
 def main():
@@ -134,6 +164,9 @@ def main():
 if __name__ == "__main__":
     if sys.argv[1:] == ["--only", "feature"]:
         feature_only()
+    elif sys.argv[1:] == ["--only", "variants"]:
+        variants()
     else:
         main()
         feature_only()
+        variants()

@@ -73,6 +73,28 @@ def dpt_feat_model_sd():
     return m, synth_state_dict_like(m)
 
 
+# g6_dpt_variants.npz (make_golden_dpt.VARIANTS): the small config with output_dim=2 on 60x75 images
+DPT_VARIANTS = {"default": dict(), "down2": dict(down_ratio=2), "nopos": dict(pos_embed=False),
+                "linear_sigmoid": dict(activation="linear", conf_activation="sigmoid"),
+                "relu_expp0": dict(activation="relu", conf_activation="expp0")}
+
+
+def dpt_variant_model_sd(name):
+    from sailrecon_amd.heads.dpt_head import DPTHead
+    from sailrecon_amd.utils.synth_weights import synth_state_dict_like
+    m = DPTHead(**DPT_SMALL, output_dim=2, **DPT_VARIANTS[name])
+    return m, synth_state_dict_like(m)
+
+
+def dpt_oracle_kwargs(cfg):
+    """Constructor keywords of a DPTHead -> keywords of oracle.sfm_oracle.dpt_forward."""
+    kw = dict(layers=DPT_SMALL["intermediate_layer_idx"])
+    for k in ("activation", "conf_activation", "pos_embed", "down_ratio", "feature_only"):
+        if k in cfg:
+            kw[k] = cfg[k]
+    return kw
+
+
 # ---------------------------------------------------------------- input formation (§8(f) rank 2)
 def pil_process_reference(arr, target, is_depth):
     """train/utils/io.py:118-153 step by step with Pillow, which is what the reference calls

@@ -145,6 +145,38 @@ def test_dpt_feature_only_matches_reference():
     assert rel_l2(feat.numpy(), g["feat"]) < 1e-5
 
 
+@pytest.mark.parametrize("name", ["default", "down2", "nopos", "linear_sigmoid", "relu_expp0"])
+def test_dpt_variants_match_reference(name):
+    """60x75 images (not multiples of 14), down_ratio, pos_embed=False and the other activations:
+    the reference's own output shape [B,S,oh,ow,...] and values."""
+    from goldens import DPT_SMALL, DPT_VARIANTS, dpt_oracle_kwargs, dpt_variant_model_sd
+    g = load_npz("g6_dpt_variants.npz")
+    _, sd = dpt_variant_model_sd(name)
+    toks = {l: torch.from_numpy(g[f"tok_{l}"]) for l in DPT_SMALL["intermediate_layer_idx"]}
+    preds, conf = O.dpt_forward(sd, "", toks, torch.from_numpy(g["images"]), 5,
+                                **dpt_oracle_kwargs(DPT_VARIANTS[name]))
+    assert preds.shape == g[f"{name}_preds"].shape and conf.shape == g[f"{name}_conf"].shape
+    assert rel_l2(preds.numpy(), g[f"{name}_preds"]) < 1e-5
+    assert rel_l2(conf.numpy(), g[f"{name}_conf"]) < 1e-5
+
+
+def test_dpt_rejects_unsupported_widths():
+    """Every conv of the head is a GEMM with 32-channel K tiles: other widths are refused by the
+    constructor (before any allocation), not in the middle of a forward."""
+    from goldens import DPT_SMALL
+    from sailrecon_amd.heads.dpt_head import DPTHead
+    for features in (96, 48):  # 96 // 2 = 48 and 48 itself are no multiples of 32
+        with pytest.raises(ValueError, match="multiples of 32"):
+            DPTHead(**{**DPT_SMALL, "features": features})
+    with pytest.raises(ValueError, match="multiples of 32"):
+        DPTHead(**{**DPT_SMALL, "out_channels": [32, 64, 100, 128]})
+    with pytest.raises(ValueError, match="multiples of 32"):
+        DPTHead(**{**DPT_SMALL, "dim_in": 250})
+    with pytest.raises(ValueError, match="output_dim >= 2"):
+        DPTHead(**DPT_SMALL, output_dim=1)
+    DPTHead(**DPT_SMALL)  # the supported widths still construct
+
+
 def test_dpt_224_matches_reference():
     from goldens import DPT_HEADS, dpt_224_inputs, rule_state_dict
     g = load_npz("g6_dpt_224.npz")

@@ -41,8 +41,8 @@ def _worker(rank, world, port, q):
                 self.aggregator = Aggregator(img_size=28, patch_size=14, embed_dim=64, depth=2, num_heads=1,
                                              patch_embed="conv", intermediate_layer_idx=[0, 1])
                 self.camera_head = CameraHead(dim_in=128, trunk_depth=1, num_heads=1)
-                self.depth_head = DPTHead(dim_in=128, output_dim=2, features=16, out_channels=[8, 16, 32, 32],
-                                          intermediate_layer_idx=[0, 1, 0, 1])
+                self.depth_head = DPTHead(dim_in=128, output_dim=2, features=64, out_channels=[32, 32, 32, 32],
+                                          intermediate_layer_idx=[0, 1, 0, 1])  # the smallest supported widths
         torch.manual_seed(100 + rank)  # different init per rank: the broadcast must unify them
         m = Small()
         tr = Trainer(m, group=dist.group.WORLD)
