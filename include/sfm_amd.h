@@ -1429,6 +1429,121 @@ int64_t sr_cloud_render_workspace(int n_views, int height, int width);
  * NULL); a workspace that is too small or not 16-byte aligned; an xform that is not 8-byte aligned. */
 int sr_cloud_render(sr_stream_t stream, const sr_cloud_render_desc* desc);
 
+/* ------------------------------------------------------------------------------------------
+ * Two-view geometry (ABI 1.16): the relative pose that the correspondences of a pair of views imply.
+ * Per pair a robust essential matrix (8-point hypotheses scored by a truncated pixel Sampson cost), its
+ * inliers, a reweighted refinement and (R, t) by cheirality.  No ground truth is read.  Everything is fp64
+ * on fp32 inputs widened exactly, nothing is contracted.  Definitions: DESIGN.md "Two-view geometry",
+ * csrc/sr_two_view.hip.  P = n_pairs, K = n_points, G = n_given, H = n_hyp, tau = threshold_px.
+ *   valid       the mask byte is non-zero and the four coordinates are finite (a test on the bits); the valid
+ *               correspondences of a pair are compacted in index order, n_valid of them
+ *   status      3: src_idx == dst_idx, or an index outside [0, n_views) (tested first; nothing is loaded
+ *               through it); 1: n_valid < 8; 2: no model has a finite cost; 0: a result.  A pair whose status
+ *               is not 0 has NaN in E, R, t, cost and pose_err, 0 in n_inliers, n_front and inlier_mask,
+ *               -1 in best and refined; with status 1 or 3 also NaN in hyp_E and hyp_cost, 0 in hyp_inliers
+ *               and -1 in hyp_idx.
+ *   x^          x = (u - cx) / fx, y = (v - cy) / fy, third entry 1; true divisions; fx, fy, cx, cy are
+ *               K[0][0], K[1][1], K[0][2], K[1][2] of the view's fp32 intrinsic (no other entry is read)
+ *   sampling    integers only, mod 2^64.  mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27;
+ *               z *= 0x94D049BB133111EB; z ^= z >> 31 (the splitmix64 finaliser).  Attempt a = 0, 1, ... of
+ *               drawn hypothesis h of pair p:  u = mix(seed + 0x9E3779B97F4A7C15 (((p 2^20 + h) 64 + a) + 1)),
+ *               j = ((u >> 32) n_valid) >> 32, the j-th valid correspondence.  j fills the next of the 8
+ *               slots if it differs from the slots already filled.  After 64 attempts the hypothesis is void.
+ *   solve       the unit null vector of the 8 rows a = x^' (x) x^ = (x'x, x'y, x', y'x, y'y, y', x, y, 1):
+ *               the eigenvector of the smallest eigenvalue of A^T A by cyclic Jacobi, as a row-major 3 x 3;
+ *               projected to the essential manifold: singular values (1, 1, 0), Frobenius norm sqrt 2, sign
+ *               free.  A void hypothesis or a non-finite result has E = NaN.
+ *   score       of model E (row-major) and valid correspondence (x, y), (x', y'), left to right as written:
+ *                 ex_r = (E[3r] x + E[3r+1] y) + E[3r+2], r = 0, 1, 2        (E x^)
+ *                 e    = (x' ex_0 + y' ex_1) + ex_2                          (x^'^T E x^)
+ *                 et_c = (E[c] x' + E[3+c] y') + E[6+c], c = 0, 1            (E^T x^')
+ *                 g    = (((ex_0 ex_0) a_0 + (ex_1 ex_1) a_1) + (et_0 et_0) a_2) + (et_1 et_1) a_3
+ *                 a    = 1 / (fx_d fx_d), 1 / (fy_d fy_d), 1 / (fx_s fx_s), 1 / (fy_s fy_s), s = src, d = dst
+ *                 r2   = (e e) / g
+ *               the squared pixel Sampson distance of sr_imc_residual_stats' v = 2 with F = K_d^-T E K_s^-1.
+ *   inlier      r2 < tau2, tau2 = tau tau, compared in fp64 (false for a NaN).  The correspondence's term of
+ *               the cost is r2 for an inlier and tau2 otherwise.
+ *   cost        the valid correspondences in chunks of 256 consecutive ones: a chunk's terms are added to 0
+ *               one by one in index order; the chunks' sums are added to 0 one by one in chunk order.
+ *               inliers = the count.  A model with a non-finite entry has cost +Inf and 0 inliers.
+ *   selection   the minimum cost, ties to the lowest model index; given models are 0 .. G - 1, drawn ones
+ *               G .. G + H - 1
+ *   refinement  rounds k = 1 .. refine_iters from the current iterate (first the selected model):
+ *               w = (1 / (t t)) / g', t = 1 + r2 / s2, g' = g with every a = 1, s2 = 4 tau2 while
+ *               k <= refine_iters / 2 and tau2 afterwards, w = 0 where it is not finite; M = sum w a a^T over
+ *               the valid correspondences (lane l of 256 adds i = l, l + 256, ... in order, then a fixed
+ *               tree); its smallest eigenvector, projected as above and scored as above.  The iterate moves on
+ *               when the new model is finite.  Every round runs.  The output is the first iterate whose cost is
+ *               the lowest and strictly below the selected model's, else the selected model (refined = 0).
+ *   decompose   U = (u1 u2 u3), V = (v1 v2 v3): v1, v2 the eigenvectors of the two largest eigenvalues of
+ *               E^T E, v3 = v1 x v2, u1 = E v1 / |E v1|, u2 = E v2 orthogonalised against u1 and normalised,
+ *               u3 = u1 x u2.  With W the rotation by 90 degrees about z the candidates are
+ *               0: (U W V^T, +u3), 1: (U W V^T, -u3), 2: (U W^T V^T, +u3), 3: (U W^T V^T, -u3).
+ *               With a = R x^, b = x^', D = (a.a)(b.b) - (a.b)(a.b) the depths of the two rays' nearest
+ *               points are lambda = ((a.b)(b.t) - (b.b)(a.t)) / D in src and mu = ((a.a)(b.t) - (a.b)(a.t)) / D
+ *               in dst; in front: D > 0, lambda > 0 and mu > 0.  The candidate with the most inliers in
+ *               front wins, ties to the lowest; n_front is its count.  X_dst = R X_src + t, |t| = 1: the
+ *               top of T = E_d E_s^-1 up to the baseline's length, and E = [t]x R up to sign.
+ *   pose_err    with R_ref = R_d R_s^T, t_ref = t_d - R_ref t_s of the fp32 ref_extrinsic (camera from
+ *               world): [0] = atan2(|(Q21 - Q12, Q02 - Q20, Q10 - Q01)| / 2, (tr Q - 1) / 2), Q = R_ref^T R;
+ *               [1] = atan2(|t_ref x t|, t_ref . t), signed: cheirality fixed t's sign; NaN if t_ref is 0.
+ *               Degrees (sr_pose_pair_errors' formulas, in fp64).
+ *   Kernels: tv_prep (per pair: validity scan, compaction, x^), tv_hyp (one lane per model: draw, solve,
+ *   project), tv_score (grid of chunks x tiles of 256 models x pairs: the chunk's x^, x^' through LDS, one
+ *   lane per model with its 9 + 4 constants in registers, broadcast reads; one partial sum per chunk and
+ *   model), tv_select (per pair: the chunk sums in order, the argmin), tv_final (per pair: refinement, mask,
+ *   decomposition, pose error).  Integer atomics on LDS counters only, no float atomics, no workgroup waits
+ *   on another: any two runs give the same bytes.  Inputs are not written.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct sr_two_view_desc {
+  const float* src_coords;    /* [P][K][2] fp32 pixels (u, v) in view src_idx[p] */
+  const float* dst_coords;    /* [P][K][2] fp32 pixels in view dst_idx[p] */
+  const uint8_t* mask;        /* [P][K] bytes, 0 = not valid, or NULL */
+  const float* intrinsic;     /* [n_views][3][3] fp32 */
+  const int32_t* src_idx;     /* [P] */
+  const int32_t* dst_idx;     /* [P] */
+  const double* given_E;      /* [P][G][9] fp64 models scored ahead of the drawn ones, or NULL (G == 0) */
+  const float* ref_extrinsic; /* [n_views][3][4] fp32, camera from world, or NULL; needed by pose_err only */
+  int n_views;                /* >= 1 */
+  int n_pairs;                /* P: 1 .. 65535 */
+  int n_points;               /* K: 1 .. 2^24, P K <= 2^31 - 1 */
+  int n_given;                /* G: 0 .. 2^20 */
+  int n_hyp;                  /* H: 0 .. 2^20, G + H >= 1 */
+  int refine_iters;           /* 0 .. 32 */
+  double threshold_px;        /* tau: finite, > 0 */
+  uint64_t seed;
+  double* E;                  /* [P][9], or NULL (as every output below) */
+  double* R;                  /* [P][9] */
+  double* t;                  /* [P][3] */
+  double* cost;               /* [P] */
+  uint32_t* n_inliers;        /* [P] */
+  uint32_t* n_front;          /* [P] */
+  int32_t* best;              /* [P] the winning model index before refinement */
+  int32_t* refined;           /* [P] the round that produced E, 0 for none */
+  int32_t* status;            /* [P] */
+  uint8_t* inlier_mask;       /* [P][K] 1 for the inliers of E, 0 elsewhere */
+  double* pose_err;           /* [P][2] degrees; needs ref_extrinsic */
+  int32_t* hyp_idx;           /* [P][H][8] the correspondences (indices into K) of every drawn hypothesis, -1 if void */
+  double* hyp_E;              /* [P][G+H][9] */
+  double* hyp_cost;           /* [P][G+H] */
+  uint32_t* hyp_inliers;      /* [P][G+H] */
+  void* workspace;            /* >= sr_two_view_workspace(...) bytes, 16-byte aligned, stream-ordered reuse */
+  int64_t workspace_bytes;
+} sr_two_view_desc;
+
+/* Bytes of workspace: per correspondence 44 (index, x^ and x^', one term), per model 84, per chunk of 256
+ * correspondences and model 12.  Never shrinks when an argument grows; 0 for arguments sr_two_view would
+ * reject. */
+int64_t sr_two_view_workspace(int n_pairs, int n_points, int n_given, int n_hyp);
+/* Five launches, asynchronous and allocation-free.  SR_EINVAL for a null desc, src_coords, dst_coords,
+ * intrinsic, src_idx, dst_idx or workspace; n_views below 1; n_pairs outside [1, 65535]; n_points outside
+ * [1, 2^24]; n_pairs * n_points above 2^31 - 1; n_given or n_hyp outside [0, 2^20]; n_given + n_hyp == 0;
+ * n_given > 0 with a NULL given_E; refine_iters outside [0, 32]; a threshold_px that is not finite or <= 0;
+ * n_pairs * (n_given + n_hyp) * ceil(n_points / 256) above 2^36; pose_err without ref_extrinsic; no output
+ * at all (hyp_idx with n_hyp == 0 is none); a workspace that is too small or not 16-byte aligned; a
+ * given_E or an fp64 output that is not 8-byte aligned. */
+int sr_two_view(sr_stream_t stream, const sr_two_view_desc* desc);
+
 #ifdef __cplusplus
 }
 #endif

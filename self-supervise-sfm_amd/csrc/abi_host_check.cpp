@@ -15,6 +15,7 @@
 //   abi_host_check layout cloud_voxel   the same for sr_sort_desc and sr_cloud_voxel_desc (ABI 1.13)
 //   abi_host_check layout sparsify   the same for sr_sparsify_desc (ABI 1.14)
 //   abi_host_check layout cloud_render   the same for sr_cloud_render_desc (ABI 1.15)
+//   abi_host_check layout two_view   the same for sr_two_view_desc (ABI 1.16)
 //   abi_host_check check    the validation sweep; exit 0 iff every call returned what it should
 #include <cstddef>
 #include <cstdio>
@@ -237,6 +238,24 @@ void layout_cloud_render() {
           FIELD(sr_cloud_render_desc, attr_fill), FIELD(sr_cloud_render_desc, depth), FIELD(sr_cloud_render_desc, index),
           FIELD(sr_cloud_render_desc, out_attr), FIELD(sr_cloud_render_desc, counts), FIELD(sr_cloud_render_desc, workspace),
           FIELD(sr_cloud_render_desc, workspace_bytes)));
+  std::printf("}\n");
+}
+
+void layout_two_view() {
+  const char* sep = "";
+  std::printf("{");
+  STRUCT(sr_two_view_desc,
+         (FIELD(sr_two_view_desc, src_coords), FIELD(sr_two_view_desc, dst_coords), FIELD(sr_two_view_desc, mask),
+          FIELD(sr_two_view_desc, intrinsic), FIELD(sr_two_view_desc, src_idx), FIELD(sr_two_view_desc, dst_idx),
+          FIELD(sr_two_view_desc, given_E), FIELD(sr_two_view_desc, ref_extrinsic), FIELD(sr_two_view_desc, n_views),
+          FIELD(sr_two_view_desc, n_pairs), FIELD(sr_two_view_desc, n_points), FIELD(sr_two_view_desc, n_given),
+          FIELD(sr_two_view_desc, n_hyp), FIELD(sr_two_view_desc, refine_iters), FIELD(sr_two_view_desc, threshold_px),
+          FIELD(sr_two_view_desc, seed), FIELD(sr_two_view_desc, E), FIELD(sr_two_view_desc, R),
+          FIELD(sr_two_view_desc, t), FIELD(sr_two_view_desc, cost), FIELD(sr_two_view_desc, n_inliers),
+          FIELD(sr_two_view_desc, n_front), FIELD(sr_two_view_desc, best), FIELD(sr_two_view_desc, refined),
+          FIELD(sr_two_view_desc, status), FIELD(sr_two_view_desc, inlier_mask), FIELD(sr_two_view_desc, pose_err),
+          FIELD(sr_two_view_desc, hyp_idx), FIELD(sr_two_view_desc, hyp_E), FIELD(sr_two_view_desc, hyp_cost),
+          FIELD(sr_two_view_desc, hyp_inliers), FIELD(sr_two_view_desc, workspace), FIELD(sr_two_view_desc, workspace_bytes)));
   std::printf("}\n");
 }
 
@@ -1295,6 +1314,132 @@ void check() {
     u = rd, u.xform = (const double*)((const char*)fake(5) + 4);
     expect("sr_cloud_render xform % 8", sr_cloud_render(nullptr, &u), false);
   }
+  {
+    // ---- sr_two_view (ABI 1.16): the workspace sweep, the planned shapes up to the launch, every rejection
+    const uint64_t inf_bits = 0x7ff0000000000000ull, nan_bits = 0x7ff8000000000000ull;
+    double inf64, nan64;
+    std::memcpy(&inf64, &inf_bits, 8), std::memcpy(&nan64, &nan_bits, 8);
+    {  // never shrinks when an argument grows; 0 for what the call rejects
+      const int ps[] = {1, 3, 70, 240, 65535}, ks[] = {1, 8, 256, 257, 10000}, gs[] = {0, 1, 5}, hs[] = {0, 1, 65, 1024};
+      for (int p : ps)
+        for (int k : ks)
+          for (int g : gs)
+            for (int h : hs) {
+              const int64_t b = sr_two_view_workspace(p, k, g, h);
+              if (g + h == 0) {
+                if (b != 0) ++g_fail;
+                continue;
+              }
+              if (b <= 0 || b % 16 || b < 44 * (int64_t)p * k + 84 * (int64_t)p * (g + h)) ++g_fail;
+              if (p < 65535 && sr_two_view_workspace(p + 1, k, g, h) < b) ++g_fail;
+              if (sr_two_view_workspace(p, k + 1, g, h) < b || sr_two_view_workspace(p, k, g + 1, h) < b ||
+                  sr_two_view_workspace(p, k, g, h + 1) < b)
+                ++g_fail;
+            }
+      if (sr_two_view_workspace(0, 8, 0, 1) || sr_two_view_workspace(65536, 8, 0, 1) || sr_two_view_workspace(1, 0, 0, 1) ||
+          sr_two_view_workspace(1, (1 << 24) + 1, 0, 1) || sr_two_view_workspace(65535, 1 << 16, 0, 1) ||
+          sr_two_view_workspace(1, 8, -1, 1) || sr_two_view_workspace(1, 8, 0, -1) || sr_two_view_workspace(1, 8, 0, (1 << 20) + 1) ||
+          sr_two_view_workspace(1, 8, (1 << 20) + 1, 0) || sr_two_view_workspace(65535, 32767, 1 << 20, 1 << 20) ||
+          sr_two_view_workspace(1, 1 << 24, 0, 1) <= 0 || sr_two_view_workspace(65535, 1, 1 << 20, 0) <= 0)
+        ++g_fail;
+      std::printf("two-view workspace bytes at 240 x 10000, 1024 models: %lld\n", (long long)sr_two_view_workspace(240, 10000, 0, 1024));
+    }
+    sr_two_view_desc td{};
+    td.src_coords = fake<float>(0), td.dst_coords = fake<float>(1), td.mask = fake<uint8_t>(2), td.intrinsic = fake<float>(3);
+    td.src_idx = fake<int32_t>(4), td.dst_idx = fake<int32_t>(5), td.given_E = fake<double>(6), td.ref_extrinsic = fake<float>(7);
+    td.n_views = 16, td.n_pairs = 240, td.n_points = 10000, td.n_given = 1, td.n_hyp = 1024, td.refine_iters = 8;
+    td.threshold_px = 2.0, td.seed = 0x123456789abcdef0ull;
+    td.E = fake<double>(8), td.R = fake<double>(9), td.t = fake<double>(10), td.cost = fake<double>(11);
+    td.n_inliers = fake<uint32_t>(12), td.n_front = fake<uint32_t>(13), td.best = fake<int32_t>(14), td.refined = fake<int32_t>(15);
+    td.status = fake<int32_t>(16), td.inlier_mask = fake<uint8_t>(17), td.pose_err = fake<double>(18), td.hyp_idx = fake<int32_t>(19);
+    td.hyp_E = fake<double>(20), td.hyp_cost = fake<double>(21), td.hyp_inliers = fake<uint32_t>(22);
+    td.workspace = fake(23), td.workspace_bytes = sr_two_view_workspace(240, 10000, 1, 1024);
+    expect("sr_two_view 240 x 10000, every output", sr_two_view(nullptr, &td), true);
+    sr_two_view_desc bare = td;
+    bare.mask = nullptr, bare.given_E = nullptr, bare.n_given = 0, bare.ref_extrinsic = nullptr, bare.pose_err = nullptr;
+    bare.R = nullptr, bare.t = nullptr, bare.cost = nullptr, bare.n_inliers = nullptr, bare.n_front = nullptr, bare.best = nullptr;
+    bare.refined = nullptr, bare.status = nullptr, bare.inlier_mask = nullptr, bare.hyp_idx = nullptr, bare.hyp_E = nullptr;
+    bare.hyp_cost = nullptr, bare.hyp_inliers = nullptr;
+    expect("sr_two_view bare, E only", sr_two_view(nullptr, &bare), true);
+    sr_two_view_desc u = bare;
+    u.E = nullptr, u.status = td.status;
+    expect("sr_two_view status only", sr_two_view(nullptr, &u), true);
+    u = td, u.n_hyp = 0, u.n_given = 5, u.refine_iters = 0, u.workspace_bytes = sr_two_view_workspace(240, 10000, 5, 0);
+    expect("sr_two_view given models only", sr_two_view(nullptr, &u), true);
+    u = td, u.n_pairs = 1, u.n_points = 1, u.n_hyp = 1, u.n_given = 0, u.refine_iters = 32;
+    expect("sr_two_view one pair, one point, one model", sr_two_view(nullptr, &u), true);
+    u = td, u.n_pairs = 65535, u.n_points = 8, u.n_hyp = 1 << 20, u.n_given = 0, u.workspace_bytes = sr_two_view_workspace(65535, 8, 0, 1 << 20);
+    expect("sr_two_view 65535 pairs, 2^20 hypotheses", sr_two_view(nullptr, &u), true);
+    u = td, u.n_pairs = 1, u.n_points = 1 << 24, u.n_hyp = 64, u.workspace_bytes = sr_two_view_workspace(1, 1 << 24, 1, 64);
+    expect("sr_two_view 2^24 correspondences", sr_two_view(nullptr, &u), true);
+    u = td, u.threshold_px = 1e-300;
+    expect("sr_two_view tiny threshold", sr_two_view(nullptr, &u), true);
+    expect("sr_two_view null desc", sr_two_view(nullptr, nullptr), false);
+    u = td, u.src_coords = nullptr;
+    expect("sr_two_view null src_coords", sr_two_view(nullptr, &u), false);
+    u = td, u.dst_coords = nullptr;
+    expect("sr_two_view null dst_coords", sr_two_view(nullptr, &u), false);
+    u = td, u.intrinsic = nullptr;
+    expect("sr_two_view null intrinsic", sr_two_view(nullptr, &u), false);
+    u = td, u.src_idx = nullptr;
+    expect("sr_two_view null src_idx", sr_two_view(nullptr, &u), false);
+    u = td, u.dst_idx = nullptr;
+    expect("sr_two_view null dst_idx", sr_two_view(nullptr, &u), false);
+    u = td, u.workspace = nullptr;
+    expect("sr_two_view null workspace", sr_two_view(nullptr, &u), false);
+    u = td, u.n_views = 0;
+    expect("sr_two_view n_views 0", sr_two_view(nullptr, &u), false);
+    u = td, u.n_pairs = 0;
+    expect("sr_two_view n_pairs 0", sr_two_view(nullptr, &u), false);
+    u = td, u.n_pairs = 65536, u.n_points = 8, u.workspace_bytes = int64_t(1) << 50;
+    expect("sr_two_view n_pairs 65536", sr_two_view(nullptr, &u), false);
+    u = td, u.n_points = 0;
+    expect("sr_two_view n_points 0", sr_two_view(nullptr, &u), false);
+    u = td, u.n_pairs = 1, u.n_points = (1 << 24) + 1, u.workspace_bytes = int64_t(1) << 50;
+    expect("sr_two_view n_points 2^24 + 1", sr_two_view(nullptr, &u), false);
+    u = td, u.n_pairs = 65535, u.n_points = 1 << 16, u.workspace_bytes = int64_t(1) << 50;
+    expect("sr_two_view 2^31 correspondences and more", sr_two_view(nullptr, &u), false);
+    u = td, u.n_given = -1;
+    expect("sr_two_view n_given -1", sr_two_view(nullptr, &u), false);
+    u = td, u.n_given = (1 << 20) + 1, u.workspace_bytes = int64_t(1) << 50;
+    expect("sr_two_view n_given 2^20 + 1", sr_two_view(nullptr, &u), false);
+    u = td, u.n_hyp = -1;
+    expect("sr_two_view n_hyp -1", sr_two_view(nullptr, &u), false);
+    u = td, u.n_hyp = (1 << 20) + 1, u.workspace_bytes = int64_t(1) << 50;
+    expect("sr_two_view n_hyp 2^20 + 1", sr_two_view(nullptr, &u), false);
+    u = td, u.n_given = 0, u.n_hyp = 0;
+    expect("sr_two_view no model", sr_two_view(nullptr, &u), false);
+    u = td, u.given_E = nullptr;
+    expect("sr_two_view n_given without given_E", sr_two_view(nullptr, &u), false);
+    u = td, u.refine_iters = -1;
+    expect("sr_two_view refine_iters -1", sr_two_view(nullptr, &u), false);
+    u = td, u.refine_iters = 33;
+    expect("sr_two_view refine_iters 33", sr_two_view(nullptr, &u), false);
+    u = td, u.threshold_px = 0.0;
+    expect("sr_two_view threshold 0", sr_two_view(nullptr, &u), false);
+    u = td, u.threshold_px = -2.0;
+    expect("sr_two_view threshold -2", sr_two_view(nullptr, &u), false);
+    u = td, u.threshold_px = nan64;
+    expect("sr_two_view threshold NaN", sr_two_view(nullptr, &u), false);
+    u = td, u.threshold_px = inf64;
+    expect("sr_two_view threshold Inf", sr_two_view(nullptr, &u), false);
+    u = td, u.n_pairs = 65535, u.n_points = 32767, u.n_given = 1 << 20, u.n_hyp = 1 << 20, u.workspace_bytes = int64_t(1) << 62;
+    expect("sr_two_view partial sums beyond 2^36", sr_two_view(nullptr, &u), false);
+    u = td, u.ref_extrinsic = nullptr;
+    expect("sr_two_view pose_err without ref_extrinsic", sr_two_view(nullptr, &u), false);
+    u = bare, u.E = nullptr;
+    expect("sr_two_view no output", sr_two_view(nullptr, &u), false);
+    u = bare, u.E = nullptr, u.hyp_idx = td.hyp_idx, u.n_hyp = 0, u.n_given = 1, u.given_E = td.given_E;
+    expect("sr_two_view no output, hyp_idx without hypotheses", sr_two_view(nullptr, &u), false);
+    u = td, u.workspace_bytes -= 1;
+    expect("sr_two_view workspace one byte short", sr_two_view(nullptr, &u), false);
+    u = td, u.workspace = (char*)fake(23) + 8;
+    expect("sr_two_view workspace % 16", sr_two_view(nullptr, &u), false);
+    u = td, u.given_E = (const double*)((const char*)fake(6) + 4);
+    expect("sr_two_view given_E % 8", sr_two_view(nullptr, &u), false);
+    u = td, u.hyp_cost = (double*)((char*)fake(21) + 4);
+    expect("sr_two_view hyp_cost % 8", sr_two_view(nullptr, &u), false);
+  }
   expect("sr_pose_decode_f32 null", sr_pose_decode_f32(nullptr, nullptr, 9, 0, 518, 518, nullptr, nullptr), false);
   expect("sr_copy_rows_f32 null", sr_copy_rows_f32(nullptr, nullptr, 0, nullptr, 0, nullptr, 0, 0), false);
   expect("sr_conv3x3_f32 null", sr_conv3x3_f32(nullptr, nullptr, 1, 8, 8, 32, 1, 0, nullptr, 32, SR_EPI_BIAS, &ep, nullptr, 32, nullptr), false);
@@ -1378,6 +1523,8 @@ int main(int argc, char** argv) {
       layout_sparsify();
     else if (argc > 2 && std::string(argv[2]) == "cloud_render")
       layout_cloud_render();
+    else if (argc > 2 && std::string(argv[2]) == "two_view")
+      layout_two_view();
     else
       layout();
     return 0;

@@ -93,7 +93,7 @@ int check_launch(const char* what) {
 
 extern "C" const char* sr_last_error(void) { return g_err; }
 extern "C" const char* sr_last_kernel(void) { return g_kernel; }
-extern "C" int sr_version(void) { return (1 << 16) | 15; }  // 1.1: sr_gemm_wgrad_pair; 1.2: sr_attention_bwd_f32; 1.3: tuning keys renumbered; 1.4: sr_gemm_epi.colsum; 1.5: sr_attention_pair_vt, sr_vt_tiles, sr_colsum_fma, sr_vec_fma2_f32; 1.6: sr_corres_sample; 1.7: sr_attention_rows; 1.8: sr_frame_groups, sr_im2col_normalize_map; 1.9: sr_pose_pair_errors, sr_pose_align; 1.10: sr_imc_residual_stats; 1.11: sr_cloud_nn, sr_cloud_nn_workspace; 1.12: sr_select_ranks, sr_select_workspace, sr_depth_eval, sr_depth_eval_workspace; 1.13: sr_sort_pairs, sr_sort_workspace, sr_cloud_voxel, sr_cloud_voxel_workspace; 1.14: sr_sparsify, sr_sparsify_workspace; 1.15: sr_cloud_render, sr_cloud_render_workspace
+extern "C" int sr_version(void) { return (1 << 16) | 16; }  // 1.1: sr_gemm_wgrad_pair; 1.2: sr_attention_bwd_f32; 1.3: tuning keys renumbered; 1.4: sr_gemm_epi.colsum; 1.5: sr_attention_pair_vt, sr_vt_tiles, sr_colsum_fma, sr_vec_fma2_f32; 1.6: sr_corres_sample; 1.7: sr_attention_rows; 1.8: sr_frame_groups, sr_im2col_normalize_map; 1.9: sr_pose_pair_errors, sr_pose_align; 1.10: sr_imc_residual_stats; 1.11: sr_cloud_nn, sr_cloud_nn_workspace; 1.12: sr_select_ranks, sr_select_workspace, sr_depth_eval, sr_depth_eval_workspace; 1.13: sr_sort_pairs, sr_sort_workspace, sr_cloud_voxel, sr_cloud_voxel_workspace; 1.14: sr_sparsify, sr_sparsify_workspace; 1.15: sr_cloud_render, sr_cloud_render_workspace; 1.16: sr_two_view, sr_two_view_workspace
 
 extern "C" int sr_set_tuning(int key, int value) {
   SR_CHECK(key >= 0 && key < SR_TUNE_COUNT, SR_EINVAL, "sr_set_tuning: unknown key %d", key);

@@ -1,9 +1,9 @@
 // Shared helpers of the evaluation kernels (sr_pose_eval, sr_cloud_eval, sr_depth_eval, sr_sort, sr_cloud_voxel,
-// sr_sparsify, sr_cloud_render): the tests on exponent bits, the fixed reduction tree, the scan and the histogram
-// slot that their contracts define "to the bit", once.  Included after sr_common.h by those seven files only.
+// sr_sparsify, sr_cloud_render, sr_two_view): the tests on exponent bits, the fixed reduction tree, the scan and the histogram
+// slot that their contracts define "to the bit", once.  Included after sr_common.h by those eight files only.
 //
 // Header code is compiled under the including object's flags, so every object keeps the semantics it had with its
-// own copy: sr_cloud_voxel.o, sr_sparsify.o and sr_cloud_render.o are built with -ffp-contract=off -fhonor-nans
+// own copy: sr_cloud_voxel.o, sr_sparsify.o, sr_cloud_render.o and sr_two_view.o are built with -ffp-contract=off -fhonor-nans
 // (the tests on the exponent bits must see NaNs there, and sr::xform_point must stay unfused), the others as they
 // always were (Makefile).
 #pragma once

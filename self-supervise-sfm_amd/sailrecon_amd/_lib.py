@@ -244,6 +244,19 @@ class CloudRenderDesc(ctypes.Structure):
     ]
 
 
+class TwoViewDesc(ctypes.Structure):
+    """sr_two_view_desc (include/sfm_amd.h)."""
+    _fields_ = [
+        ("src_coords", _vp), ("dst_coords", _vp), ("mask", _vp), ("intrinsic", _vp), ("src_idx", _vp), ("dst_idx", _vp),
+        ("given_E", _vp), ("ref_extrinsic", _vp), ("n_views", _i32), ("n_pairs", _i32), ("n_points", _i32),
+        ("n_given", _i32), ("n_hyp", _i32), ("refine_iters", _i32), ("threshold_px", ctypes.c_double),
+        ("seed", ctypes.c_uint64), ("E", _vp), ("R", _vp), ("t", _vp), ("cost", _vp), ("n_inliers", _vp),
+        ("n_front", _vp), ("best", _vp), ("refined", _vp), ("status", _vp), ("inlier_mask", _vp), ("pose_err", _vp),
+        ("hyp_idx", _vp), ("hyp_E", _vp), ("hyp_cost", _vp), ("hyp_inliers", _vp), ("workspace", _vp),
+        ("workspace_bytes", _i64),
+    ]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "sr_last_error": (ctypes.c_char_p, []),
@@ -357,6 +370,8 @@ _PROTOS = {
     "sr_sparsify": (_i32, [_vp, ctypes.POINTER(SparsifyDesc)]),
     "sr_cloud_render_workspace": (_i64, [_i32, _i32, _i32]),
     "sr_cloud_render": (_i32, [_vp, ctypes.POINTER(CloudRenderDesc)]),
+    "sr_two_view_workspace": (_i64, [_i32, _i32, _i32, _i32]),
+    "sr_two_view": (_i32, [_vp, ctypes.POINTER(TwoViewDesc)]),
 }
 EXPORTED = tuple(_PROTOS)
 

@@ -1789,6 +1789,85 @@ def cloud_render(points: Tensor, extrinsic: Tensor, intrinsic: Tensor, hw, *, at
     check(_lib.load().sr_cloud_render(_stream(points), ctypes.byref(d)), "sr_cloud_render")
 
 
+# ---------------------------------------------------------------- two-view geometry (utils/two_view.py)
+def two_view_workspace_bytes(n_pairs: int, n_points: int, n_given: int, n_hyp: int) -> int:
+    """sr_two_view_workspace (0 for arguments sr_two_view rejects)."""
+    args = [int(v) for v in (n_pairs, n_points, n_given, n_hyp)]
+    if not all(-2 ** 31 <= v < 2 ** 31 for v in args):
+        return 0
+    return int(_lib.load().sr_two_view_workspace(*args))
+
+
+def two_view(src_coords: Tensor, dst_coords: Tensor, intrinsic: Tensor, src_idx: Tensor, dst_idx: Tensor, *,
+             mask: Optional[Tensor] = None, given_E: Optional[Tensor] = None, ref_extrinsic: Optional[Tensor] = None,
+             n_hyp: int = 1024, threshold_px: float = 2.0, refine_iters: int = 8, seed: int = 0,
+             E: Optional[Tensor] = None, R: Optional[Tensor] = None, t: Optional[Tensor] = None,
+             cost: Optional[Tensor] = None, n_inliers: Optional[Tensor] = None, n_front: Optional[Tensor] = None,
+             best: Optional[Tensor] = None, refined: Optional[Tensor] = None, status: Optional[Tensor] = None,
+             inlier_mask: Optional[Tensor] = None, pose_err: Optional[Tensor] = None, hyp_idx: Optional[Tensor] = None,
+             hyp_E: Optional[Tensor] = None, hyp_cost: Optional[Tensor] = None,
+             hyp_inliers: Optional[Tensor] = None) -> None:
+    """sr_two_view: ``src_coords`` / ``dst_coords`` [P, K, 2] fp32 pixels of the views ``src_idx`` / ``dst_idx`` [P]
+    int32 with ``intrinsic`` [V, 3, 3] fp32; ``mask`` [P, K] uint8; ``given_E`` [P, G, 9] fp64 models scored ahead of
+    the ``n_hyp`` drawn ones; ``ref_extrinsic`` [V, 3, 4] fp32 for ``pose_err``.  Outputs (all optional, contiguous, of
+    exactly the stated sizes): ``E`` / ``R`` [P, 9], ``t`` [P, 3], ``cost`` [P], ``pose_err`` [P, 2], ``hyp_E``
+    [P, G + H, 9], ``hyp_cost`` [P, G + H] fp64; ``n_inliers`` / ``n_front`` [P], ``hyp_inliers`` [P, G + H] int32
+    (storage of the unsigned counts); ``best`` / ``refined`` / ``status`` [P], ``hyp_idx`` [P, H, 8] int32;
+    ``inlier_mask`` [P, K] uint8."""
+    if not isinstance(src_coords, Tensor) or src_coords.dtype != torch.float32 or src_coords.dim() != 3 \
+            or src_coords.shape[2] != 2 or not src_coords.is_contiguous() or src_coords.numel() == 0:
+        raise ValueError("src_coords must be a contiguous fp32 [P, K, 2] tensor")
+    dev = src_coords.device
+    P, K = int(src_coords.shape[0]), int(src_coords.shape[1])
+    if not isinstance(dst_coords, Tensor) or dst_coords.dtype != torch.float32 or dst_coords.shape != src_coords.shape \
+            or not dst_coords.is_contiguous() or dst_coords.device != dev:
+        raise ValueError(f"dst_coords must be a contiguous fp32 [{P}, {K}, 2] tensor on {dev}")
+    if not isinstance(intrinsic, Tensor) or intrinsic.dtype != torch.float32 or intrinsic.dim() != 3 \
+            or tuple(intrinsic.shape[1:]) != (3, 3) or intrinsic.shape[0] == 0 or not intrinsic.is_contiguous() \
+            or intrinsic.device != dev:
+        raise ValueError(f"intrinsic must be a contiguous fp32 [V, 3, 3] tensor on {dev}")
+    V = int(intrinsic.shape[0])
+    G = 0
+    if given_E is not None:
+        if not isinstance(given_E, Tensor) or given_E.dtype != torch.float64 or given_E.dim() != 3 \
+                or given_E.shape[0] != P or given_E.shape[2] != 9 or not given_E.is_contiguous() or given_E.device != dev:
+            raise ValueError(f"given_E must be a contiguous fp64 [{P}, G, 9] tensor on {dev}")
+        G = int(given_E.shape[1])
+    H = int(n_hyp)
+    M = G + H
+    if ref_extrinsic is not None and (not isinstance(ref_extrinsic, Tensor) or ref_extrinsic.dtype != torch.float32
+                                      or tuple(ref_extrinsic.shape) != (V, 3, 4) or not ref_extrinsic.is_contiguous()
+                                      or ref_extrinsic.device != dev):
+        raise ValueError(f"ref_extrinsic must be a contiguous fp32 [{V}, 3, 4] tensor on {dev}")
+    need = two_view_workspace_bytes(P, K, G, H)
+    if need <= 0:
+        raise ValueError(f"{P} pairs of {K} correspondences with {G} given and {H} drawn models are outside the ranges")
+    _out(src_idx, "src_idx", torch.int32, P, src_coords)
+    _out(dst_idx, "dst_idx", torch.int32, P, src_coords)
+    if src_idx is None or dst_idx is None:
+        raise ValueError("src_idx and dst_idx are needed")
+    _out(mask, "mask", torch.uint8, P * K, src_coords)
+    f64, i32 = torch.float64, torch.int32
+    for name, ten, dt, cnt in (("E", E, f64, 9 * P), ("R", R, f64, 9 * P), ("t", t, f64, 3 * P), ("cost", cost, f64, P),
+                               ("n_inliers", n_inliers, i32, P), ("n_front", n_front, i32, P), ("best", best, i32, P),
+                               ("refined", refined, i32, P), ("status", status, i32, P),
+                               ("inlier_mask", inlier_mask, torch.uint8, P * K), ("pose_err", pose_err, f64, 2 * P),
+                               ("hyp_idx", hyp_idx, i32, 8 * P * H), ("hyp_E", hyp_E, f64, 9 * P * M),
+                               ("hyp_cost", hyp_cost, f64, P * M), ("hyp_inliers", hyp_inliers, i32, P * M)):
+        _out(ten, name, dt, cnt, src_coords)
+    d = _lib.TwoViewDesc()
+    ws = torch.empty(need, device=dev, dtype=torch.uint8)  # stream-ordered: the caching allocator's rule
+    d.src_coords, d.dst_coords, d.mask, d.intrinsic = _p(src_coords), _p(dst_coords), _p(mask), _p(intrinsic)
+    d.src_idx, d.dst_idx, d.given_E, d.ref_extrinsic = _p(src_idx), _p(dst_idx), _p(given_E), _p(ref_extrinsic)
+    d.n_views, d.n_pairs, d.n_points, d.n_given, d.n_hyp, d.refine_iters = V, P, K, G, H, int(refine_iters)
+    d.threshold_px, d.seed = float(threshold_px), int(seed) & (2 ** 64 - 1)
+    d.E, d.R, d.t, d.cost, d.n_inliers, d.n_front = _p(E), _p(R), _p(t), _p(cost), _p(n_inliers), _p(n_front)
+    d.best, d.refined, d.status, d.inlier_mask, d.pose_err = _p(best), _p(refined), _p(status), _p(inlier_mask), _p(pose_err)
+    d.hyp_idx, d.hyp_E, d.hyp_cost, d.hyp_inliers = _p(hyp_idx), _p(hyp_E), _p(hyp_cost), _p(hyp_inliers)
+    d.workspace, d.workspace_bytes = _p(ws), need
+    check(_lib.load().sr_two_view(_stream(src_coords), ctypes.byref(d)), "sr_two_view")
+
+
 # ---------------------------------------------------------------- training step (SURVEY §8(f) rank 4)
 _TRAIN_WS = {}  # ((device, stream), name) -> fp32 workspace
 
